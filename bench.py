@@ -9,6 +9,10 @@ gathers them (RCCL, torch.distributed "nccl") into the full linear framebuffer.
 
     python bench.py [--gpus N --steps K --warmup W]
     torchrun --nproc-per-node N bench.py --gpus N ...   (one process per GPU)
+
+A plain run sets up, warms up, times the K steps and prints the headline line. --full adds what takes runs
+of its own: the other precision's line, the rooflines, the CPU baseline (the oracle on host cores) and the
+parity legs against it. --dump-outputs DIR writes the last timed step's framebuffer to DIR/framebuffer.npy.
 """
 import argparse
 import glob
@@ -496,6 +500,23 @@ def roofline(key, st, segs, my_samples, elapsed, kern, fp64):
     return roof
 
 
+DUMP_MAX_BYTES = 48 << 20  # --dump-outputs writes at most this much
+
+
+def dump_outputs(outdir, fb, W, H):
+    """--dump-outputs: the framebuffer the last timed step left in rank 0's host memory, in its own dtype, as
+    outdir/framebuffer.npy: (H, W, 3), or, for a frame over DUMP_MAX_BYTES, the (n, 3) pixels at a fixed
+    seeded sample of linear pixel indices (ascending; the same for every run of the same frame size)."""
+    px = fb.numpy().reshape(H * W, 3)
+    n = DUMP_MAX_BYTES // (3 * px.itemsize)
+    if H * W > n:
+        px = px[np.sort(np.random.default_rng(20240229).choice(H * W, n, replace=False))]
+    else:
+        px = px.reshape(H, W, 3)
+    os.makedirs(outdir, exist_ok=True)
+    np.save(os.path.join(outdir, "framebuffer.npy"), np.ascontiguousarray(px))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -522,8 +543,13 @@ def main():
     ap.add_argument("--cpu-msamples", type=float, default=600.0,
                     help="size of the CPU-baseline row sample (Msamples of oracle work)")
     ap.add_argument("--alt-steps", "--f64-steps", type=int, default=10, dest="alt_steps",
-                    help="after the headline run, time this many frames of the other precision on the same "
-                         "config (f32 after an f64 headline and vice versa); 0 = skip")
+                    help="--full: after the headline run, time this many frames of the other precision on the "
+                         "same config (f32 after an f64 headline and vice versa); 0 = skip")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline run also: the other precision's line, the rooflines, the CPU baseline "
+                         "and the parity legs against the oracle. Without it only the headline is measured")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's framebuffer (rank 0's host copy) to DIR/framebuffer.npy")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -628,8 +654,10 @@ def main():
     kern = "k_step" if args.segments_per_launch > 0 else "k_persist"
     alt_name = "f32" if args.precision == "f64" else "f64"
     alt_prec = abi.RT_PREC_F32 if alt_name == "f32" else abi.RT_PREC_F64
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, fb, W, H)
     alt_run = None
-    if args.alt_steps > 0:
+    if args.full and args.alt_steps > 0:
         alt_run = run(alt_prec, args.alt_steps, 1, args.kernel_timing == "on")
 
     if rank == 0:
@@ -642,10 +670,10 @@ def main():
         # moves ~0.1 % of the classic wavefront's bytes. achieved = VALU work per launch (rocprofv3
         # counters of this build and workload, profiles/*_pmc.json) / live launch time.
         roof = None
-        if args.kernel_timing == "on":
+        if args.full and args.kernel_timing == "on":
             roof = roofline(key, st, segs, my_samples, elapsed, kern, prec == abi.RT_PREC_F64)
         cpu = parity = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             threads = args.cpu_threads or cpu_threads()[0]
             # C4: lit 16x16 tiles (the reference's x-median tree renders ~2 rows of the stand-in in the
             # budget, and those rows are near-black); the other configs: evenly spaced full rows
@@ -687,6 +715,7 @@ def main():
             if args.config == "c2" else f"Msamples/sec (pixels*spp) {scene_name} {W}x{H}@{spp}spp",
             "value": round(value, 2), "unit": "Msamples/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True,
+            "full": args.full,
             "scaling": "strong", "vs_baseline": None, "dtype": "fp32" if prec == abi.RT_PREC_F32 else "fp64",
             "data": asset or "synthetic (the reference's scene, procedurally built; no assets)",
             "config": {"workload": f"{scene_name} {W}x{H} {spp}spp depth {depth}, light sampling on",
