@@ -13,8 +13,8 @@ ARCH     ?= gfx950
 # 51.0 -> 49.7, C5 fp32 1,249 -> 1,179 (r04f)
 HIPFLAGS ?= -O3 -std=c++17 -fPIC -Wall -ffp-contract=on -fno-slp-vectorize --offload-arch=$(ARCH)
 
-LIB_SRCS := $(PKG)/csrc/rt_kernels.hip $(PKG)/csrc/rt_multi.hip $(PKG)/csrc/scene_compile.cpp
-LIB_HDRS := $(PKG)/csrc/rt_device.h $(PKG)/csrc/rt_sin.h $(PKG)/csrc/rt_scene.h $(PKG)/csrc/scene_compile.h include/rt_hip.h
+LIB_SRCS := $(PKG)/csrc/rt_kernels.hip $(PKG)/csrc/rt_render.hip $(PKG)/csrc/rt_multi.hip $(PKG)/csrc/scene_compile.cpp
+LIB_HDRS := $(PKG)/csrc/rt_device.h $(PKG)/csrc/rt_types.h $(PKG)/csrc/rt_launch.h $(PKG)/csrc/rt_plan.h $(PKG)/csrc/rt_sin.h $(PKG)/csrc/rt_scene.h $(PKG)/csrc/scene_compile.h include/rt_hip.h
 
 CXX      ?= g++
 CXXFLAGS ?= -O2 -std=c++17 -fPIC -Wall -Wextra -Wno-unused-parameter
@@ -22,8 +22,8 @@ RT_HDRS  := $(wildcard $(PKG)/rt/*.h) include/rt_hip.h
 
 all: $(BUILD)/librt_hip.so $(BUILD)/librt_scenes.so $(BUILD)/rt_main tools/valu_rates tools/l1_rates oracle
 
-# one object per source, so a host-only change does not recompile the kernels
-LIB_OBJS := $(BUILD)/obj/rt_kernels.o $(BUILD)/obj/rt_multi.o $(BUILD)/obj/scene_compile.o
+# one object per source, so a change to the host code (rt_render.hip) does not recompile the kernels (rt_kernels.hip)
+LIB_OBJS := $(BUILD)/obj/rt_kernels.o $(BUILD)/obj/rt_render.o $(BUILD)/obj/rt_multi.o $(BUILD)/obj/scene_compile.o
 $(BUILD)/obj/%.o: $(PKG)/csrc/%.hip $(LIB_HDRS)
 	@mkdir -p $(BUILD)/obj
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<

@@ -11,6 +11,7 @@
 
 #include "rt_scene.h"
 #include "rt_sin.h"
+#include "rt_types.h"
 
 namespace rtd {
 
@@ -18,32 +19,11 @@ namespace rtd {
 #ifndef RT_BIG_SPHERE_R
 #define RT_BIG_SPHERE_R 16
 #endif
-#ifndef RT_WIDE_SPEC  // wide BVH in HBM: speculative while-while traversal (trace_wide)
-#define RT_WIDE_SPEC 1
-#endif
-// RT_WIDE_FMA (retired in round 6, always on): fp64 rays over the wide BVH: octant-ordered planes, one fma per plane
-// distance
-// RT_WIDE_OCT32 (retired in round 6, always on): fp32 rays over the wide BVH: octant-ordered planes, (p - o) * inv (C3
-// fp32 60.87 -> 57.22 ms/frame, C4 351.9 -> 341.6)
-// RT_WIDE_HALF_F64 (retired in round 6, always on): fp64 rays over trees in HBM read the fp16 node form (rt_scene.h
-// WNodeH): 5 loads per node visit instead of 7 (C4 fp64 504.0 -> 480.8 ms/frame; fp32 rays lose, see WNodeH)
-#ifndef RT_WIDE_FMA32  // fp32 rays over an LDS tree: one fma per plane distance, three per-ray constants and one
-#define RT_WIDE_FMA32 1  // bound (trace_wide; C3 fp32 49.63 -> 48.54 ms/frame; 2, per-axis constants: 49.01)
-#endif
-// RT_WIDE_OFS64 (retired in round 6, always on): fp64 rays keep 64-bit addresses into trees in HBM (C4 fp64: 32-bit
-// offsets 573.5 ms/frame, 64-bit 545.1; fp32 the other way round, 340.7 -> 329.1)
-// RT_WIDE_PREFETCH (retired in round 6, always on): a triangle's words loaded with the record's first word (C4 358.9 ->
-// 357.2 ms)
 // The extended (CAMX) kernels' heavy, rarely taken code -- fp64 OCML trigonometry (sphere_uv, the fisheye
 // camera), the noise textures -- as real calls (round 5): inlined, their temporaries sized the whole kernel
 // (~290 registers, 1 wave per SIMD); called, the loop keeps its own budget and the live state is saved
 // around the call only when it is taken.
 #define RT_EXT_FN __device__ __attribute__((noinline))
-#ifndef RT_MIX_SELECT  // the light / material halves of the mixture pdf (pdf.h:52-56) as one select path: 1 in
-#define RT_MIX_SELECT 1  // the flat program (C2 fp64 28.33 -> 28.15 ms/frame, fp32 18.83 -> 18.49, r05e), 2 in every kernel
-#endif
-// RT_LIGHT_PDF_F64 (retired in round 6, always on): fp64 axis-aligned light pdf by one reciprocal (light_pdf_aligned,
-// round 4)
 
 // Math policy. fp64 (the parity path): libm where the reference calls it (log), and division,
 // reciprocal and square root refined from the hardware estimates to about an ulp (below).
@@ -160,18 +140,14 @@ __device__ __forceinline__ double flog(double x) { return log(x); }
 // heaviest path) held the fp64 kernels at 2-3 waves per SIMD. Within an ulp or two of
 // sin(fl(2 pi u)): far inside the fp64 parity tolerance (1e-9 relative against the oracle).
 // Round 4: a 1024-entry table of (sin, cos)(2 pi j / 1024), correctly rounded on the host (rt_kernels.hip
-// sincos_table_init), and the angle addition formulas for the rest, delta = 2 pi (u - j / 1024) < 2 pi / 1024:
+// upload_sincos_table), and the angle addition formulas for the rest, delta = 2 pi (u - j / 1024) < 2 pi / 1024:
 // sin delta = delta (1 - delta^2 / 6 + delta^4 / 120) and cos delta - 1 = delta^2 (-1/2 + delta^2 / 24 -
 // delta^4 / 720) leave truncation errors below 1e-19, so the result is within about an ulp, like
 // OCML's sincospi, at one table read and 13 fp64 operations instead of ~22 fp64 and ~20 other VALU
 // operations (and the polynomial constants OCML's version kept in 18 VGPRs across the path loop).
 // u * 1024 and its fractional part are exact for every double u in [0, 1).
-constexpr int kSinCosTab = 1024;
 __device__ double2 g_sincos_tab[kSinCosTab];
 __device__ __forceinline__ void sincos2pi(double u, double& s, double& c) {
-#ifdef RT_OCML_SINCOS
-  sincospi(2.0 * u, &s, &c);
-#else
   const double t = u * double(kSinCosTab);
   const double h = floor(t);
   const double2 sc = g_sincos_tab[(uint32_t)(int32_t)h & (kSinCosTab - 1)];
@@ -181,7 +157,6 @@ __device__ __forceinline__ void sincos2pi(double u, double& s, double& c) {
   const double cm1 = d2 * fma(d2, fma(d2, -1.0 / 720.0, 1.0 / 24.0), -0.5);
   s = fma(sc.y, sd, fma(sc.x, cm1, sc.x));
   c = fma(-sc.x, sd, fma(sc.y, cm1, sc.y));
-#endif
 }
 // x / pi (pdf.h:27-29 cosine_pdf::value): fp32 as before, fp64 as a product with 1/pi
 __device__ __forceinline__ float div_pi(float x) { return fdiv(x, 3.14159265358979323846f); }
@@ -190,11 +165,7 @@ __device__ __forceinline__ float pow5(float x) { return (x * x) * (x * x) * x; }
 // material.h:131 std::pow(1 - cosine, 5), as products (a few ulp; OCML's pow is a log/exp pair)
 __device__ __forceinline__ double pow5(double x) { return (x * x) * (x * x) * x; }
 
-// ------------------------------------------------------------------ vectors
-template <class R>
-struct V {
-  R x, y, z;
-};
+// ------------------------------------------------------------------ vectors (V: rt_types.h)
 template <class R>
 __device__ __forceinline__ V<R> mkv(R x, R y, R z) {
   return {x, y, z};
@@ -292,30 +263,7 @@ struct Num<double> {
   static constexpr double box_slack() { return 1.0 + 2.0 * 3.0 * 1.1102230246251565e-16; }
 };
 
-// ------------------------------------------------------------------ counter RNG
-// 32-bit draw for (seed, pixel, sample, dim); identical to the oracle's
-// (oracle/oracle.cpp) and to rt_rng_u32 on the host.
-__host__ __device__ __forceinline__ uint32_t mix32(uint32_t x) {
-  x ^= x >> 16;
-  x *= 0x21f0aaadu;
-  x ^= x >> 15;
-#ifndef RT_EXP_CHEAPMIX  // timing experiment only (wrong images)
-  x *= 0xd35a2d97u;
-  x ^= x >> 15;
-#endif
-  return x;
-}
-__host__ __device__ __forceinline__ uint32_t key_pixel(uint64_t seed, uint32_t pixel) {
-  return mix32(pixel ^ mix32((uint32_t)seed ^ 0x9E3779B9u));
-}
-__host__ __device__ __forceinline__ uint32_t key_sample(uint64_t seed, uint32_t sample) {
-  return mix32(sample + mix32((uint32_t)(seed >> 32) + 0x7F4A7C15u));
-}
-// the key of one camera sample; each draw is then a single mix (two 32-bit multiplies)
-__host__ __device__ __forceinline__ uint32_t key_path(uint32_t ka, uint32_t kb) { return mix32(ka ^ kb); }
-__host__ __device__ __forceinline__ uint32_t draw_u32(uint32_t ks, uint32_t dim) {
-  return mix32(ks + dim * 0x9E3779B9u);
-}
+// ------------------------------------------------------------------ counter RNG (keys and draws: rt_types.h)
 template <class R>
 __device__ __forceinline__ R to_unit(uint32_t x) {  // exact 24-bit value in [0,1)
   return R(x >> 8) * R(1.0 / 16777216.0);
@@ -334,106 +282,9 @@ struct Keys {
   uint32_t ks;  // key_path of the camera sample
 };
 
-// ------------------------------------------------------------------ scene view
-// A word of the wide BVH's primitive stream (rt_scene.h WNode): 16 bytes of floats in the fp32
-// blob, 32 bytes of doubles in the fp64 one (same word indices, so the leaf codes are shared); the
-// primitive's entry is in the bits of w (the low 32 bits of the double).
-template <class R>
-struct WWord;
-template <>
-struct WWord<float> {
-  using T = float4;
-};
-struct alignas(32) double4w {
-  double x, y, z, w;
-};
-template <>
-struct WWord<double> {
-  using T = double4w;
-};
+// ------------------------------------------------------------------ scene view (DevScene, CamDev, WWord: rt_types.h)
 __device__ __forceinline__ uint32_t wentry(const float4& h) { return __float_as_uint(h.w); }
 __device__ __forceinline__ uint32_t wentry(const double4w& h) { return (uint32_t)__double_as_longlong(h.w); }
-
-// The camera as camera::render/generate_ray use it (camera.h:137-141, 244-290), in double.
-struct CamDev {
-  int32_t mode;  // rt_camera_mode
-  int32_t pad;
-  V<double> pos, du, dv;
-  V<double> dir00;   // perspective / fisheye: f dir - vw/2 right + vh/2 up + (du + dv)/2 (camera.h:246, 260)
-  V<double> pos00;   // orthonormal / lens: pos - vw/2 right + vh/2 up + (du + dv)/2 (camera.h:253, 278)
-  V<double> dir;     // dir_, unit
-  V<double> fdir;    // focus_dist_ * dir_ (camera.h:279)
-  V<double> disk_u, disk_v;  // defocus_disk_u/v (camera.h:129-131)
-  double focal;      // focal_length_ (camera.h:266)
-};
-
-template <class R>
-struct DevScene {
-  const Quad<R>* quads;
-  const Sphere<R>* spheres;
-  const Tri<R>* tris;
-  const Instance<R>* insts;
-  const Volume<R>* vols;
-  const Node<R>* nodes;
-  const uint32_t* refs;
-  const Material<R>* mats;
-  const Texture<R>* texs;
-  const Light<R>* light;
-  const LinRec<R>* lin;  // linear program (n_linear > 0)
-  uint32_t n_linear;
-  const FlatQuadT<R>* flatq;  // flat program (has_flat): quads grouped by plane axis, then boxes
-  const FlatBoxT<R>* flatb;
-  uint32_t n_flatq[3], n_flatb;
-  uint32_t n_mats;
-  int32_t has_flat;
-  uint32_t root;
-  int32_t background;
-  int32_t has_volumes;
-  uint32_t n_nodes;
-  const double* texdata;  // procedural-texture tables (Texture::data)
-  const uint8_t* images;  // picture-texture pixels (Texture::data)
-  int32_t has_procedural; // any perlin / value / worley / voronoi texture: the EXT kernels
-  // wide BVH (rt_scene.h WNode; float boxes in both blobs): nodes, primitive words, root code,
-  // stack need, WK_* kinds
-  const WNode* wnodes;
-  const typename WWord<R>::T* wprims;
-  uint32_t n_wnodes, n_wprim_words, wroot, wide_stack, wide_kinds;
-  int32_t has_wide;
-  uint32_t wide_big;  // primitives at the head of the word stream, tested before the tree
-  uint32_t wide_top;  // nodes [0, wide_top): the tree's first levels (HBM trees: read from an LDS copy)
-  const WNodeH* wnodesh;  // the fp16 form of the tree (rt_scene.h WNodeH; 0: none)
-  const Quad<double>* quads64;  // fp32 scenes: the fp64 quads (RT_QUAD_REFINE; 0: none)
-  // the render's camera when it is perspective (0: another model): near-edge quad hits of camera rays are re-decided
-  // on the fp64 camera ray (quad_edge64)
-  const CamDev* cam64;
-  // a tree in HBM keeps at most wide_lds_stack<R>() stack entries per lane in LDS; deeper entries go to
-  // wide_spill[(depth - wide_lds_stack<R>()) * spill_lanes + lane]
-  uint32_t* wide_spill;
-  uint32_t spill_lanes;
-};
-// RT_WIDE_TOP (retired in round 6, always on): fp32 rays over trees in HBM: the tree's first levels read from LDS
-// (trace_wide)
-#ifndef RT_WIDE_TOP_N  // at most this many of them (the builder orders up to kWideTopMax breadth-first)
-#define RT_WIDE_TOP_N 55
-#endif
-// RT_WIDE_TOP_F64 (retired in round 6, always on): the same for fp64 rays, whose HBM trees are read in the fp16 form
-// (WNodeH)
-#ifndef RT_WIDE_TOP_N_F64
-#define RT_WIDE_TOP_N_F64 85
-#endif
-#ifndef RT_WIDE_LDS_STACK
-#define RT_WIDE_LDS_STACK 12
-#endif
-#ifndef RT_WIDE_LDS_STACK_F64  // 18 since round 6: the fp64 LL kernel's LDS also holds the throughput (Path LT)
-#define RT_WIDE_LDS_STACK_F64 18
-#endif
-// stack entries per lane kept in LDS for a tree in HBM, by ray precision (fp32: fewer, so the LDS also holds
-// the top of the tree and 8 blocks fit a CU; C4 fp32, stack / top nodes / waves: 24 / 0 / 6 309.4 ms/frame,
-// 22 / 21 / 6 290.1, 16 / 47 / 7 268.8, 14 / 63 / 7 268.1, 12 / 55 / 8 265.2; r05r-r05u)
-template <class R>
-constexpr uint32_t wide_lds_stack() {
-  return sizeof(R) == 4 ? RT_WIDE_LDS_STACK : RT_WIDE_LDS_STACK_F64;
-}
 
 // World -> object through an instance chain (hittable.h:75-82, 125-135, 192-202, 259-270).
 template <class R>
@@ -522,9 +373,18 @@ __device__ __forceinline__ bool quad_test(V<R> n, R D, V<R> q, V<R> qa, V<R> qb,
 // The fp64 ray is the path's own camera ray when the ray is one (bounce 0, world space, a perspective camera):
 // camera rays are built in fp64 (begin_sample) and rounded, so the oracle's edge decision is then reproduced up to
 // the fp64 arithmetic; for later bounces the fp32 ray itself, whose origin is the fp32 path's own hit point.
-#ifndef RT_QUAD_REFINE
-#define RT_QUAD_REFINE 1
-#endif
+
+// The direction of a perspective (and, before its bending, a fisheye) camera ray (camera.h:246-250, 260-261),
+// in two parts: the pixel's, the same for every sample of a work item, and the sample's offset within
+// the pixel. The one definition begin_sample, camera_ray and quad_edge64 use, so a camera ray rebuilt
+// elsewhere is bit-identical to the path's own. Left-associated, as the reference. (x, y: integers or doubles)
+template <class X>
+__device__ __forceinline__ V<double> persp_pixel(V<double> dir00, V<double> du, V<double> dv, X x, X y) {
+  return (dir00 + double(x) * du) + double(y) * dv;
+}
+__device__ __forceinline__ V<double> persp_sample(V<double> base, V<double> du, V<double> dv, double ox, double oy) {
+  return (base + ox * du) + oy * dv;
+}
 // what quad_edge64 rebuilds the camera ray from: the path key and pixel (begin_sample), the bounce
 struct EdgeRay {
   uint32_t ks, xy, bounce;
@@ -532,11 +392,11 @@ struct EdgeRay {
 RT_EXT_FN bool quad_edge64(const Quad<double>* q64, const CamDev* cam, V<float> o, V<float> d, float tmin, float tmax,
                            EdgeRay er) {
   V<double> od = mkv((double)o.x, (double)o.y, (double)o.z), dd = mkv((double)d.x, (double)d.y, (double)d.z);
-  if (cam != nullptr && er.bounce == 0) {  // begin_sample's ray (camera.h:245-251, 293), same operations
+  if (cam != nullptr && er.bounce == 0) {  // begin_sample's ray (camera.h:245-251, 293)
     const double ox = to_unit<double>(draw_u32(er.ks, 0)) - 0.5, oy = to_unit<double>(draw_u32(er.ks, 1)) - 0.5;
     const double x = double(er.xy & 0xFFFFu), y = double(er.xy >> 16);
     od = cam->pos;
-    dd = ((cam->dir00 + x * cam->du) + y * cam->dv + ox * cam->du) + oy * cam->dv;
+    dd = persp_sample(persp_pixel(cam->dir00, cam->du, cam->dv, x, y), cam->du, cam->dv, ox, oy);
   }
   const Quad<double>& q = *q64;
   double t64;
@@ -570,7 +430,7 @@ template <class R>
 __device__ __forceinline__ bool quad_t_near(const DevScene<R>& sc, uint32_t i, V<R> o, V<R> d, R tmin, R tmax, R& t,
                                             EdgeRay er, bool world) {
   const Quad<R>& q = sc.quads[i];
-  if constexpr (sizeof(R) == 4 && RT_QUAD_REFINE) {
+  if constexpr (sizeof(R) == 4) {
     const Quad<double>* q64 = sc.quads64;
     return quad_test_near(ld3(q.n), q.D, ld3(q.q), ld3(q.a), ld3(q.b), o, d, tmin, tmax, t, q64 != nullptr,
                           [&](float t0, float t1) {
@@ -1240,16 +1100,16 @@ __device__ __forceinline__ bool trace_wide(const DevScene<R>& sc, const unsigned
   // constants cost the fp32 kernels, at their tighter register budgets, more spills than the fmas
   // save (C4 fp32 351 -> 460 ms/frame; fp64 C3 89.8 -> 81.7, C4 561 -> 545), so fp32 keeps
   // (p - o) * inv, octant-ordered (RT_WIDE_OCT32: C3 fp32 60.9 -> 57.2, C4 351.9 -> 341.6).
-  // RT_WIDE_FMA32 (round 4): fp32 rays form p * inv + c too, with c = -o * inv rounded and ONE per-ray
+  // kFma32 (round 4; C3 fp32 49.63 -> 48.54 ms/frame): fp32 rays over an LDS tree form p * inv + c too, with c = -o * inv rounded and ONE per-ray
   // bound instead of six constants: each distance is within |o_a * inv_a| 2^-24 of (p - o) * inv
   // (c's rounding; the fma's own is relative, covered by box_slack), so the test tn <= tf * slack +
   // 2 e with e = max_a |o_a inv_a| 2^-23 accepts every box the exact test accepts. An infinite or NaN
   // o_a * inv_a (a zero direction component) gives planes of the right sign or NaN, and no bound.
   // Over a tree in HBM (C4 stand-in) the one bound culls too little: a ray with a small direction
   // component has a large o_a * inv_a, and the bound then widens every axis (C4 fp32 310.7 -> 378.5
-  // ms/frame; C3 49.8 -> 48.8). RT_WIDE_FMA32=2: per-axis constants, as the fp64 rays'.
-  constexpr bool kFma = (F64) || (!F64 && LDSN && RT_WIDE_FMA32 == 2);
-  constexpr bool kFma32 = !F64 && LDSN && RT_WIDE_FMA32 == 1;
+  // ms/frame; C3 49.8 -> 48.8). Per-axis constants as the fp64 rays' were slower there (C3 fp32 49.01).
+  constexpr bool kFma = F64;
+  constexpr bool kFma32 = !F64 && LDSN;
   constexpr bool kOct = kFma || kFma32 || (!F64);
   [[maybe_unused]] const uint32_t onx0 = (__float_as_uint(inv.x) >> 31) * 48u,
                                  ony0 = 16u + (__float_as_uint(inv.y) >> 31) * 48u,
@@ -1486,27 +1346,18 @@ __device__ __forceinline__ bool trace_wide(const DevScene<R>& sc, const unsigned
     ry.fresh = 0;
   }
   bool done = false;
-#ifdef RT_WIDE_DEBUG_LONG
-  uint32_t dbg_visits = 0;
-#endif
   // Speculative while-while (Aila & Laine 2009), for trees in HBM: a lane that reaches a leaf
   // postpones it and keeps traversing until every traversing lane of the wave holds one, so the
   // leaf tests run with the wave's lanes together instead of a few at a time, and node fetches
   // overlap. The postponed leaf is tested with the tmax of its time. C4 stand-in 459.6 -> 426.4
   // ms/frame; the LDS-resident C3 tree, whose node visits are cheap and whose leaves hold up to 6
   // spheres, lost (62.2 -> 63.6: nodes visited past a postponed leaf are not culled by its hits).
-  if constexpr (!LDSN && RT_WIDE_SPEC) {
+  if constexpr (!LDSN) {
   bool have = true;  // cur holds a node or a leaf still to visit
   for (;;) {
     uint32_t leaf = 0u;  // the postponed leaf (a leaf code is never 0)
     while (have) {
       RT_WIDE_STAT(0);
-#ifdef RT_WIDE_DEBUG_LONG  // development: a traversal far longer than the tree warrants
-      if (++dbg_visits == 20000u)
-        printf("[long] o=(%.17g %.17g %.17g) d=(%.17g %.17g %.17g) inv=(%g %g %g) w=(%g %g %g) tmax=%g sp=%d cur=%u\n",
-               (double)ro.x, (double)ro.y, (double)ro.z, (double)rd.x, (double)rd.y, (double)rd.z, inv.x, inv.y, inv.z,
-               wx, wy, wz, (double)tmax, sp, cur);
-#endif
       if (cur & kLeafBit) {
         if (leaf) break;  // a second leaf: test the first, come back with this one
         leaf = cur;
@@ -2133,7 +1984,7 @@ __device__ __forceinline__ double light_pdf_aligned(const double* f, V<double> o
   const double dd = d.x * d.x + d.y * d.y + d.z * d.z;
   return ((th * th) * dd) * (dd * frsq_nz(dd)) * fabs(rA) * f[7];
 }
-// SEL: the fp32 sampled directions (dir from light_random) by select, not a branch (RT_MIX_SELECT)
+// SEL: the fp32 sampled directions (dir from light_random) by select, not a branch (shade kMixSel)
 template <class R, bool SEL = false>
 __device__ __forceinline__ R light_pdf(const Light<R>* Lp, V<R> o, V<R> dir, bool sampled = false) {
   const int32_t kind = ld_here(&Lp->kind);

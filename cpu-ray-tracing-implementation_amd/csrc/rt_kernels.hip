@@ -1,67 +1,32 @@
-// rt_kernels.hip -- wavefront path tracer for MI355X (gfx950) + the C ABI of include/rt_hip.h.
+// rt_kernels.hip -- the kernels of the wavefront path tracer for MI355X (gfx950) and the functions that
+// launch them (rt_launch.h). The host side -- contexts, render(), the C ABI -- is rt_render.hip.
 //
-// The reference's per-pixel/per-sample loop (camera.h:154-172) and recursive
-// ray_color (camera.h:193-241) become P path slots. Default schedule (k_persist):
-// one launch of as many lanes as the chip holds resident, each keeping its path in
-// registers and pulling work items from per-XCD dequeue heads. Wavefront schedule (segments_per_launch = K > 0): the slots'
-// state lives in HBM as structure-of-arrays (16-byte records per slot, coalesced
-// dwordx4 access) between launches:
-//
-//   k_init    first camera ray of every slot            (camera.h:244-251)
-//   repeat:
-//     k_step    every live slot advances up to K segments: closest hit
-//               (camera.h:198, world.hit), then emission + scatter + mixture
-//               pdf (camera.h:199-240), or finish the sample and regenerate the
-//               next camera ray of the slot's work item (pixel, chunk of samples)
-//     every kBatch rounds: k_count/k_scan/k_compact build the live-slot queue
-//     (wave __ballot + block prefix sums) once half the pool has drained
-//   k_resolve  per-pixel mean over the chunks, in chunk order (camera.h:169-170)
-//
-// Work item = (pixel, chunk of C consecutive samples); a wavefront slot s owns items
-// s, s + P, s + 2P, ... Each sample's random numbers are keyed by
-// (seed, global pixel, sample) so the image is bit-identical for any pool size,
+// The reference's per-pixel/per-sample loop (camera.h:154-172) and recursive ray_color (camera.h:193-241)
+// become P path slots (Schedules). Default schedule: k_persist, one launch of as many lanes as the
+// chip holds resident, each keeping its path in registers and pulling work items (pixel, chunk of samples) from
+// per-XCD dequeue heads. Wavefront schedule (segments_per_launch = K > 0): the slots' state lives in HBM between
+// launches -- k_init, then k_step (every live slot advances up to K segments) with k_count / k_scan / k_compact
+// rebuilding the live-slot queue. k_resolve: the per-pixel mean over the chunks, in chunk order. Each sample's
+// random numbers are keyed by (seed, global pixel, sample), so the image is bit-identical for any pool size,
 // tiling or GPU count.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <map>
-#include <tuple>
 #include <mutex>
-#include <new>
-#include <stdexcept>
-#include <string>
-#include <vector>
+#include <tuple>
 
 #include "../../include/rt_hip.h"
 #include "rt_device.h"
-#include "scene_compile.h"
+#include "rt_launch.h"
 
 using namespace rtd;
 
 namespace {
 
-constexpr int kBlock = 256;
-// RT_BG_BLACK_SKIP (retired in round 6, always on): shade: no unit-sphere test for a miss against a solid black
-// background
-// RT_BG_SOLID_FAST (retired in round 6, always on): shade: nor against another solid background when |d| < 500 (the
-// test always hits)
 #ifndef RT_LINEAR_WAVES
 #define RT_LINEAR_WAVES 6
-#endif
-// RT_SPHERE_REFINE (retired in round 6, always on): fp32 sphere hits: point and normal from an fp64 re-solve (shade)
-// RT_COLD_LDS (retired in round 6, always on): the volume linear program: the cold path state in LDS (Path, LC)
-// RT_COLD_LDS_F64 (retired in round 6, always on): the same for the fp64 volume program (round 4)
-// RT_LINEAR_NORAD (retired in round 6, always on): the volume programs: emission added straight into the item's running
-// sum (Path NORAD)
-// RT_F64_TAIL (retired in round 6, always on): 1: fp64 renders use the fp32 item layout (bulk + tail items); 0: uniform
-// items of 16
-#ifndef RT_PERSIST_MODE  // 2: dynamic (per-XCD heads), 1: static striding (development A/B)
-#define RT_PERSIST_MODE 2
 #endif
 #ifndef RT_STACK_WAVES  // 4: the LDS limit of the LDS-node BVH kernel (32.8 KB per block); C3 151 -> 129 ms vs 3
 #define RT_STACK_WAVES 4
@@ -76,128 +41,28 @@ constexpr int kBlock = 256;
                              // 128 VGPRs) 1661 ms/frame, 5: 1567, 6: 2594 (spills); round 4 (cold state in LDS,
 #define RT_LINEAR_VOL_WAVES 6  // radiance folded, table sin/cos): 5: 1,326, 6: 1,247
 #endif
-// RT_LIN_LLI (retired in round 6, always on): the volume program for lambertian + isotropic + light scenes (shade LL,
-// LLI): C5 fp32 1,189 -> 1,124 ms/frame, fp64 2,358 -> 2,262 (r05y)
-// the LLI volume program's fp32 form at 7 waves per SIMD (72 VGPRs + 36 B spilled; 79 VGPRs at 6): 1,124 -> 1,097
-// ms/frame (r05y). 8 waves (64 VGPRs + 60 B spilled) was 1.6 % faster (r05v2; r06a 1,070 against 1,094 ms) but its
-// scratch -- 60 B for each of 8,192 waves' 64 lanes, 31 MB, about the L2s' size -- went to memory: 78.6 GB of writes
-// per launch (r06a PMC) against 2.2 GB at 7 waves, where the partial sums are ~1.2 GB. Round 6 keeps 7.
+// the LLI volume program (lambertian + isotropic + light scenes, shade LL, LLI: C5 fp32 1,189 -> 1,124 ms/frame,
+// fp64 2,358 -> 2,262, r05y), its fp32 form at 7 waves per SIMD (72 VGPRs + 36 B spilled; 79 VGPRs at 6): 1,124 ->
+// 1,097 ms/frame (r05y). 8 waves (64 VGPRs + 60 B spilled) was 1.6 % faster (r05v2; r06a 1,070 against 1,094 ms) but
+// its scratch -- 60 B for each of 8,192 waves' 64 lanes, 31 MB, about the L2s' size -- went to memory: 78.6 GB of
+// writes per launch (r06a PMC) against 2.2 GB at 7 waves, where the partial sums are ~1.2 GB. Round 6 keeps 7.
 #ifndef RT_LINEAR_VOL_WAVES_LLI
 #define RT_LINEAR_VOL_WAVES_LLI 7
 #endif
 #ifndef RT_LINEAR_VOL_WAVES_F64  // the fp64 volume program (round 4, cold state in LDS): 3 waves 2,672 ms/frame, 4: 2,400
 #define RT_LINEAR_VOL_WAVES_F64 4
 #endif
-constexpr int kBatch = 16;           // extend/shade rounds between live-slot counts
-constexpr int kSegShards = 256;      // segment counter shards
-constexpr uint32_t kAutoPool32 = 1u << 21;
-constexpr uint32_t kAutoPool64 = 1u << 19;
-constexpr uint32_t kAutoChunk = 16;
-// The automatic item sizes (rt_render_params.samples_per_item = 0); RT_ITEM_* in the environment
-// override them for A/B runs (scripts/dev_tail.py)
-static uint32_t env_u32(const char* name, uint32_t dflt) {
-  const char* v = std::getenv(name);
-  return (v && *v) ? (uint32_t)std::strtoul(v, nullptr, 10) : dflt;
-}
-static double env_f64(const char* name, double dflt) {
-  const char* v = std::getenv(name);
-  return (v && *v) ? std::strtod(v, nullptr) : dflt;
-}
-// Bulk items: 8 samples (32 for the flat program, whose samples are cheap); at most
-// kMaxItemsPerPixel items per pixel in all (both sizes doubled until they fit), so a high-spp frame
-// (C5: 3840x2160 at 4096 spp) keeps its item count under 2^31 and its partial sums bounded.
-// Measured (ms/frame, full frame / one rank of eight, scripts/dev_tail.sh): C3 16 samples 62.5 /
-// 12.0, 8 with the last half in items of 4 61.2 / 8.9; C2 32 uniform 23.9 / 3.59, 32 with the last
-// eighth in items of 8 23.6 / 3.47, with the last quarter 23.7-23.9 / 3.38 (the one-GPU frame, the
-// headline, is kept).
-constexpr uint32_t kMaxItemsPerPixel = 256;
-// items a frame should have at least (render(); RT_ITEMS_TARGET overrides). C1 (400x400, 64 spp), ms/frame
-// by target (item size): fp64 none (16) 0.918, 1 M (8) 0.792, 2.5 M (4) 0.735, 5 M (2) 0.710; fp32 none
-// (32 + tail items of 8) 0.661, 1 M 0.589, 2.5 M 0.525, 5 M 0.536. The BASELINE configs from C2 up have
-// 40 M items or more and keep their sizes.
-constexpr uint32_t kItemsTarget = 4000000;
-// item partial sums of one pass at most (render(): a call needing more renders its chunks in passes)
-constexpr uint64_t kPartialBudget = 2ull << 30;
-constexpr uint32_t kMinAutoChunk = 2;
-static uint32_t auto_chunk(bool flat) {
-  return std::max(1u, flat ? env_u32("RT_ITEM_CHUNK_FLAT", 2 * kAutoChunk) : env_u32("RT_ITEM_CHUNK", kAutoChunk / 2));
-}
-static uint32_t auto_tail_chunk(bool flat) {
-  return std::max(1u, flat ? env_u32("RT_ITEM_TAIL_CHUNK_FLAT", 8) : env_u32("RT_ITEM_TAIL_CHUNK", 4));
-}
-static double auto_tail_frac(bool flat) {
-  return std::min(1.0, std::max(0.0, flat ? env_f64("RT_ITEM_TAIL_FRAC_FLAT", 0.125) : env_f64("RT_ITEM_TAIL_FRAC", 0.5)));
-}
-constexpr int kAutoSegments = 16;  // segments each slot advances per k_step launch
-// persistent schedule: upper bound of the grid's lanes. The dynamic schedule (persist 2) cuts the
-// grid to what the chip holds resident; the static one (persist 1) launches them all (~10x the
-// resident lanes: blocks that start late balance the uneven per-lane work)
-constexpr uint32_t kAutoPersistLanes = 1u << 22;
-
-// dynamic persistent schedule (persist 2): items are handed out in batches of kQBatch; batch j of
-// head h is batch number j * kHeads + h of the item space, so the heads interleave over the whole
-// frame and a head that runs dry steals from the others. Against static striding (persist 1) the
-// tail shrinks to one item: C2 28.6 -> 26.5 ms on one GPU, 4.07 -> 3.70 ms for one rank of eight.
-constexpr uint32_t kHeads = 8;
-constexpr uint32_t kHeadStride = 64;  // 256 B apart: one L2 line per head
-constexpr uint32_t kQBatch = 64;
+constexpr uint32_t kQBatch = 64;  // items a wave takes from a head at a time (rt_launch.h kHeads)
 constexpr uint32_t kNoItem = 0xFFFFFFFFu;
 
-template <class R>
-struct alignas(4 * sizeof(R)) R4 {
-  R x, y, z, w;
-};
-
-// Path state in HBM, one entry per slot, structure of arrays of 16-byte (fp32)
-// or 32-byte (fp64) records so every access is a coalesced dwordx4:
-//   O  origin, ray time            D  direction, bounce (-1: slot retired)
-//   T  throughput                  L  radiance of the running sample
-//   A  running sum of the item     S  key_pixel, key of the running sample, item, sample
-//   X  the surface the ray leaves (entry, instance): self-intersection exclusion;
-//      the pixel (x | y << 16) and the end of the sample range of the slot's item
 // utility.h:46-52 random_in_unit_disk by rejection; attempt k draws dimensions kDimDisk + 2k
 // and + 2k + 1 (far above the per-bounce dimensions); the origin after kDiskTries failures
 // (probability (1 - pi/4)^64 ~ 1e-43). Same as the oracle.
 constexpr uint32_t kDimDisk = 0x7FFF0000u, kDiskTries = 64;
 
+// The kernels' argument: LaunchParams as a type of this translation unit, like the kernels themselves.
 template <class R>
-struct Params {
-  DevScene<R> sc;
-  R4<R>* O;
-  R4<R>* D;
-  R4<R>* T;
-  R4<R>* L;
-  R4<R>* A;
-  uint4* S;
-  uint4* X;
-  R* partial;              // per item: 3 sums
-  const uint32_t* pixmap;  // local pixel -> its image position x | y << 16
-  const uint32_t* queue;   // live slots, or null = slots [0, n)
-  uint32_t n;
-  uint32_t P, npix, n_items, chunk, spp, first_sample, W;
-  // two item sizes: chunks [0, k_bulk) hold `chunk` samples, the later ones (the frame's last
-  // items in dequeue order) `tail_chunk` <= chunk samples each
-  uint32_t k_bulk, tail_chunk;
-  // the render's chunks come in passes (render(): the partial sums of one pass fit a memory budget): this
-  // launch's items are chunks [chunk0, chunk0 + n_items / npix) of every pixel
-  uint32_t chunk0;
-  uint64_t npix_m;  // item / npix = (item * npix_m) >> npix_k for every item < 2^31 (div_magic)
-  uint32_t npix_k;
-  int32_t max_depth;
-  uint64_t seed;
-  // camera rays are built in fp64 for both paths (fp32 rounds once), from CamDev in device
-  // memory (scalar loads at the point of use)
-  int32_t cam_mode;
-  const CamDev* camx;
-  unsigned long long* seg_shards;
-  int32_t K;  // segments per launch
-  // persistent mode (k_persist): one launch. 1: lanes stride over the items by P; 2 (default):
-  // the grid is what the chip holds resident and lanes pull items from the per-XCD heads
-  int32_t persist;
-  uint32_t* heads;  // kHeads dequeue counters, kHeadStride words apart (persist 2)
-  uint64_t seg_cap;  // a lane never needs more segments than this (its items * chunk * max_depth)
-  uint32_t* fault;   // set when a lane hits seg_cap (internal error, reported by the host)
-};
+struct Params : LaunchParams<R> {};
 
 // The per-lane words of the path state that only sample and item boundaries touch (LC paths,
 // below), in LDS as [word][lane]: 32-bit words, then the fp64 pixel base as [component][lane].
@@ -316,9 +181,10 @@ struct Path {
 };
 static_assert(Path<float>::kXy < kColdWords, "cold words");
 
-// The pixel's part of the perspective camera ray, (dir00 + x du) + y dv (camera.h:246-250): the
-// same for every sample of a work item, so it is computed once per item (and once per k_step
-// launch), not once per sample. Same operations in the same order: bit-identical.
+// The pixel's part of the perspective camera ray: the same for every sample of a work item, so it is
+// computed once per item (and once per k_step launch), not once per sample. persp_pixel's expression, written
+// out so that each field is loaded where it is used (as a call, whose arguments are loaded first, the k_step
+// kernels' schedule moves).
 template <class R, class PS>
 __device__ __forceinline__ void pixel_base(const Params<R>& p, PS& s, uint32_t xy) {
   if constexpr (!PS::kLean) {
@@ -429,7 +295,7 @@ __device__ __forceinline__ uint32_t next_item_dyn(const Params<R>& p) {
 }
 
 // An item's first sample and the end of its sample range: bulk items of p.chunk samples, then tail
-// items of p.tail_chunk (the item layout, render()). `lchunk`: the item's chunk within this pass (item =
+// items of p.tail_chunk (the item layout, rt_plan.h). `lchunk`: the item's chunk within this pass (item =
 // lchunk * npix + the pixel's index); the layout is decided by the frame's chunk, lchunk + chunk0.
 template <class R>
 __device__ __forceinline__ void item_range(const Params<R>& p, uint32_t item, uint32_t& lchunk, uint32_t& first,
@@ -517,7 +383,7 @@ RT_EXT_FN void camera_ray(const CamDev* cp, uint32_t ks, uint32_t x, uint32_t y,
     tm = 0;  // ray(origin, direction): time 0, no draw
   } else {  // fisheye (camera.h:259-275)
     const V<double> dir = ld_uniform(&cp->dir, 0);
-    d = ((ld_uniform(&cp->dir00, 0) + double(x) * du) + double(y) * dv + ox * du) + oy * dv;
+    d = persp_sample(persp_pixel(ld_uniform(&cp->dir00, 0), du, dv, x, y), du, dv, ox, oy);
     const V<double> w = d - dir;
     const double r = sqrt(w.x * w.x + w.y * w.y + w.z * w.z);
     const double theta = asin(r / ld_uniform(&cp->focal, 0));
@@ -543,10 +409,10 @@ __device__ __forceinline__ void begin_sample(const Params<R>& p, PS& s) {
   if (!CAMX || p.cam_mode == RT_CAM_PERSPECTIVE) {  // camera.h:245-251
     const V<double> du = ld_here(&p.camx->du), dv = ld_here(&p.camx->dv);
     if constexpr (!PS::kLean) {
-      d = (s.cb() + ox * du) + oy * dv;
-    } else {  // the same operations in the same order as pixel_base + the above: bit-identical
+      d = persp_sample(s.cb(), du, dv, ox, oy);
+    } else {  // no kept pixel base: pixel_base's value, recomputed
       const uint32_t xy = s.xy(), x = xy & 0xFFFFu, y = xy >> 16;
-      d = ((ld_here(&p.camx->dir00) + double(x) * du) + double(y) * dv + ox * du) + oy * dv;
+      d = persp_sample(persp_pixel(ld_here(&p.camx->dir00), du, dv, x, y), du, dv, ox, oy);
     }
     tm = to_unit<double>(draw_u32(s.ks, 2));
   } else if constexpr (CAMX) {
@@ -600,12 +466,28 @@ __global__ __launch_bounds__(kBlock) void k_init(Params<R> p) {
 // and there is no importance-sampling light (RTOW, C3; host-checked): the emission, gloss, isotropic and
 // light-mixture code is compiled out.
 // LLI (with LL): isotropic phase materials too (the lm record's w is 2; C5's smoke volumes)
-template <class R, bool CAMX, bool FLAT = false, bool MOVING = true, bool MLDS = false, bool LL = false,
-          bool NL = false, bool LLI = false, class PS>
+// What shade compiles in comes as one configuration type. ShadeOf<Trav>: the form a traversal policy's persistent
+// kernel takes; ShadeGeneral: every material and light, materials from global memory (k_step, whose register
+// budget the special forms' LDS tables would squeeze).
+template <class Trav>
+struct ShadeOf {
+  static constexpr bool kFlat = Trav::kFlat, kMoving = Trav::kMoving, kLL = Trav::kLL, kNL = Trav::kNL,
+                        kLLI = Trav::kLLI;
+  static constexpr bool kMatsLds = Trav::kTablesLds || Trav::kLL;
+};
+template <bool FLAT>
+struct ShadeGeneral {
+  static constexpr bool kFlat = FLAT, kMoving = true, kLL = false, kNL = false, kLLI = false, kMatsLds = false;
+};
+template <class R, bool CAMX, class Cfg, class PS>
 __device__ bool shade(const Params<R>& p, PS& s, R t, uint32_t e, int32_t inst, uint32_t nm = 0,
                       const Material<R>* mats = nullptr, const R4<R>* lm = nullptr) {
+  constexpr bool FLAT = Cfg::kFlat, MOVING = Cfg::kMoving, MLDS = Cfg::kMatsLds, LL = Cfg::kLL, NL = Cfg::kNL,
+                 LLI = Cfg::kLLI;
   const DevScene<R>& sc = p.sc;
-  constexpr bool kMixSel = RT_MIX_SELECT == 2 || (RT_MIX_SELECT == 1 && FLAT);
+  // the light / material halves of the mixture pdf (pdf.h:52-56) as one select path, in the flat program (C2 fp64
+  // 28.33 -> 28.15 ms/frame, fp32 18.83 -> 18.49, r05e); in every kernel it lost on C5 (fp64 2,226 ms, r06c)
+  constexpr bool kMixSel = FLAT;
   V<R> add = mkv(R(0), R(0), R(0));
   bool has_add = false, done = false;
   V<R> new_o = s.o, new_d = s.d;
@@ -947,7 +829,8 @@ __device__ bool shade(const Params<R>& p, PS& s, R t, uint32_t e, int32_t inst, 
     dst[1] = acc.y;
     dst[2] = acc.z;
     s.set_acc(mkv(R(0), R(0), R(0)));
-    const uint32_t nx = p.persist == 2 ? next_item_dyn(p) : (item + p.P < p.n_items ? item + p.P : kNoItem);
+    // persistent schedule: from the wave's queue; wavefront schedule: the slot's next item, P further on
+    const uint32_t nx = p.persist == kPersist ? next_item_dyn(p) : (item + p.P < p.n_items ? item + p.P : kNoItem);
     if (nx == kNoItem) {
       s.bounce = -1;
       return false;
@@ -966,24 +849,31 @@ __device__ bool shade(const Params<R>& p, PS& s, R t, uint32_t e, int32_t inst, 
 // (extend, camera.h:198), then shade. Traversal: the wave-uniform linear
 // program (small scenes) or the BVH stack machine with a per-lane LDS stack.
 // LLI: a lambertian + isotropic + light scene (shade LL, LLI; C5's Cornell box with smoke volumes)
+// What the traversal policies below have in common; each declares only what differs.
+struct TravDefaults {
+  static constexpr bool kFlat = false;       // the flat program (trace_flat; shade FLAT)
+  static constexpr bool kWide = false;       // the wide BVH (resumable traversal: Trav::steps)
+  static constexpr bool kTablesLds = false;  // the flat program's records and materials in LDS (Trav::Tables)
+  struct Tables {};
+  static constexpr int kStack = 0;           // the binary BVH's LDS stack entries per lane
+  static constexpr int kLdsNodes = 0;        // the binary BVH's nodes copied into LDS, at most
+  static constexpr uint32_t kLdsMats = 16;   // materials the LL kernels' LDS table holds
+  // the scene class shade is compiled for (ShadeOf): lambertian + light, no light, LL + isotropic; moving spheres
+  [[maybe_unused]] static constexpr bool kLL = false, kNL = false, kLLI = false, kMoving = true;
+  // the path state (Path): lean, no radiance register, cold fields in LDS, throughput in LDS
+  [[maybe_unused]] static constexpr bool kLean = false, kNoRad = false, kColdLds = false, kThrLds = false;
+};
 template <class R, bool SPH, bool TRI, bool VOL, bool LLI = false>
-struct LinearTrav {
-  static constexpr bool kLL = LLI;
-  static constexpr bool kLinLL = LLI;
-  static constexpr uint32_t kLdsMats = 16;
-  static constexpr int kStack = 0;
+struct LinearTrav : TravDefaults {
+  static constexpr bool kLL = LLI, kLLI = LLI;
   // waves per SIMD the register budget is cut for (occupancy hides the shading loads); the
   // lean quad-only program fits 96 VGPRs with a small spill, the others would spill heavily
   static constexpr int kWaves = sizeof(R) != 4 ? (VOL ? RT_LINEAR_VOL_WAVES_F64 : RT_LINEAR_WAVES_F64)
                                  : (!SPH && !TRI && !VOL) ? RT_LINEAR_WAVES
                                  : (!SPH && !TRI && VOL)  ? (LLI ? RT_LINEAR_VOL_WAVES_LLI : RT_LINEAR_VOL_WAVES)
                                                           : 1;
-  static constexpr int kLdsNodes = 0;
-  static constexpr bool kFlat = false;
-  static constexpr bool kWide = false;
-  // the volume program's registers (C5: 23 -> 6 VGPRs spilled at 96, 1563 -> 1498 ms/frame)
-  static constexpr bool kTablesLds = false;
-  static constexpr bool kLean = false;  // (LLI lean: 7 waves 1,094 -> 1,117 ms/frame; 8 waves 48 B spilled, r06a)
+  // the volume program's registers (C5: 23 -> 6 VGPRs spilled at 96, 1563 -> 1498 ms/frame); not lean (LLI lean: 7
+  // waves 1,094 -> 1,117 ms/frame; 8 waves 48 B spilled, r06a)
   static constexpr bool kNoRad = VOL;
   static constexpr bool kColdLds = VOL;
   static constexpr bool kThrLds = VOL && LLI && sizeof(R) == 4;  // (Path LT: C5 fp32 1,091 -> 1,072 ms/frame, r06d)
@@ -997,40 +887,28 @@ struct LinearTrav {
 #ifndef RT_FLAT_WAVES
 #define RT_FLAT_WAVES 8
 #endif
-// RT_F64_COLD_LDS (retired in round 6, always on): fp64 flat program: the cold path state (item sum, pixel, keys,
-// camera base) in LDS
-// RT_FLAT_LDS (retired in round 6, always on): flat program (persistent kernels): records and materials copied into LDS
+#ifndef RT_FLAT_WAVES_F64  // fp64 flat program: waves per SIMD the register budget is cut for (1: none)
+#define RT_FLAT_WAVES_F64 5
+#endif
 #ifndef RT_FLAT_WAVES_F64_LL  // the same for the lambertian + light kernel
 #define RT_FLAT_WAVES_F64_LL 7  // C2 fp64: 5 waves 28.90 ms/frame, 6: 28.08 (r05c; the general kernel at 5: 31.28);
                                 // 7 (72 VGPRs + 32 B spilled, from 80): 27.94 -> 27.79 (r05w7); 8 does not fit
 #endif
-// RT_FLAT_LL (retired in round 6, always on): flat program: a kernel for lambertian + light scenes (shade LL)
-// RT_FLAT_NORAD (retired in round 6, always on): flat program: emission added straight into the item's running sum
-// (Path NORAD)
-#ifndef RT_FLAT_WAVES_F64  // fp64 flat program: waves per SIMD the register budget is cut for (1: none)
-#define RT_FLAT_WAVES_F64 5
-#endif
 template <class R, bool TLDS = false, bool LL = false>
-struct FlatTrav {
-  static constexpr bool kLinLL = false;
+struct FlatTrav : TravDefaults {
+  static constexpr bool kFlat = true;
   static constexpr bool kTablesLds = TLDS;  // persistent kernel: Tables in LDS (fill, run_lds)
   static constexpr bool kLL = LL;           // lambertian + light scene (shade LL; the lm table)
-  static constexpr int kStack = 0;
   static constexpr int kWaves = sizeof(R) == 4 ? RT_FLAT_WAVES : (LL ? RT_FLAT_WAVES_F64_LL : RT_FLAT_WAVES_F64);
-  static constexpr int kLdsNodes = 0;
-  static constexpr bool kFlat = true;
-  static constexpr bool kWide = false;
-  // fp32: 72 -> 64 VGPRs, but C2 23.5 -> 24.1 ms/frame; fp64: see RT_F64_COLD_LDS
-  static constexpr bool kLean = false;
+  // not lean (fp32: 72 -> 64 VGPRs, but C2 23.5 -> 24.1 ms/frame)
   static constexpr bool kNoRad = true;  // 6 VGPRs in fp64 (its item sum is in LDS)
   static constexpr bool kColdLds = sizeof(R) == 8;
-  static constexpr bool kThrLds = false;
   template <class PS>
   __device__ __forceinline__ static void run(const DevScene<R>& sc, const Node<R>*, const PS& s, Keys, uint32_t*,
                                              R& t, uint32_t& e, int32_t& i, uint32_t& nm) {
     trace_flat<R>(sc, s.o, s.d, s.xe, s.xi, t, e, i, nm, sc.flatq, sc.flatb);
   }
-  // the scene's small tables copied into LDS (persistent kernel, RT_FLAT_LDS): the hit's record and
+  // the scene's small tables copied into LDS (persistent kernel): the hit's record and
   // material are then LDS reads instead of dependent global loads
   // (the LL kernel's tables are smaller, so a 256-lane block's LDS -- tables plus the fp64 cold path state,
   // ~27 KB with the general sizes -- leaves room for 6 blocks per CU)
@@ -1068,18 +946,10 @@ struct FlatTrav {
 // every traversal step reads LDS instead of waiting on the memory hierarchy (RTOW: 117 nodes)
 constexpr uint32_t kLdsNodeMax = 256;
 template <class R, int STACK, bool LDSN = false>
-struct StackTrav {
-  static constexpr bool kLL = false, kLinLL = false;
+struct StackTrav : TravDefaults {  // (no cold state in LDS: its LDS holds the traversal stacks)
   static constexpr int kStack = STACK;
   static constexpr int kLdsNodes = LDSN ? (int)kLdsNodeMax : 0;
   static constexpr int kWaves = sizeof(R) == 4 ? RT_STACK_WAVES : (LDSN ? 1 : RT_STACK_WAVES_F64);  // occupancy over a small spill
-  static constexpr bool kFlat = false;
-  static constexpr bool kWide = false;
-  static constexpr bool kTablesLds = false;
-  static constexpr bool kLean = false;
-  static constexpr bool kNoRad = false;
-  static constexpr bool kColdLds = false;  // its LDS holds the traversal stacks
-  static constexpr bool kThrLds = false;
   template <class PS>
   __device__ __forceinline__ static void run(const DevScene<R>& sc, const Node<R>* nodes, const PS& s, Keys k,
                                              uint32_t* stk, R& t, uint32_t& e, int32_t& i, uint32_t&) {
@@ -1095,15 +965,6 @@ struct StackTrav {
 #ifndef RT_WIDE_WAVES  // LDS-resident tree (C3: 4 waves 93.6 ms, 5: 86.2, 6: 83.0; with leaves of 6 spheres the
 #define RT_WIDE_WAVES 7  // block needs ~21 KB, so 7 fit a CU: 64.0 -> 62.2 despite 22 spilled VGPRs; 8: 67.8)
 #endif
-#ifndef RT_WIDE_WAVES_GLOBAL  // tree in HBM, 32-bit stack in LDS (C4 stand-in: 4 waves 519 ms, 5: 462; with the
-// speculative traversal 5: 424, 6: 412.5 -- 7 blocks of 24 KB stacks do not fit the 160 KB LDS)
-#define RT_WIDE_WAVES_GLOBAL 8  // round 5, with 12 LDS stack entries and 55 top nodes in LDS (wide_lds_stack)
-#endif
-// RT_WIDE_TRIQUAD (retired in round 6, always on): a kernel for triangle + quad scenes (else the all-kinds kernel): C4
-// 358.9 -> 353.8 ms
-// RT_PARAM_RELOAD (retired in round 6, always on): flat / linear / binary-BVH loops: parameters reloaded per segment
-// RT_WIDE_RELOAD (retired in round 6, always on): round 4 (lean state): C3 fp32 51.9 -> 51.1 ms/frame, fp64 71.3 ->
-// 70.7, C4 neutral
 #ifndef RT_SHADE_BATCH  // < 64: a wave stops traversing to shade once this many of its lanes have finished
 #define RT_SHADE_BATCH 48  // (LDS-resident tree, C3 fp32 ms/frame: never 57.06, 48: 52.57, 52: 52.58, 56: 52.81, 60: 53.57; fp64 81.3 -> 75.8)
 #endif
@@ -1122,32 +983,20 @@ struct StackTrav {
 #ifndef RT_WIDE_WAVES_F64_NL  // the NL form over an LDS tree, fp64 (116 VGPRs at 4 waves)
 #define RT_WIDE_WAVES_F64_NL 5  // C3 fp64 at 4 waves 69.07 ms/frame, 5: 65.41 (r05q; the general kernel at 4: 70.23)
 #endif
-// RT_WIDE_NL (retired in round 6, always on): a wide kernel for sphere scenes without a light (shade NL)
-// RT_WIDE_LL (retired in round 6, always on): a wide kernel for lambertian + light triangle/quad scenes (shade LL)
-// RT_WIDE_LEAN (retired in round 6, always on): the wide kernels keep the lean path state (Path LEAN)
-// LL: a lambertian + light scene (shade LL; the material table `Lm` in static LDS)
+// LL: a lambertian + light scene (shade LL; the material table in static LDS); NL: no light (shade NL)
 template <class R, bool SPH, bool TRI, bool QUAD, bool MOV, bool LDSN, bool LL = false, bool NL = false>
-struct WideTrav {
-  static constexpr bool kLL = LL;
-  static constexpr bool kLinLL = false;
-  static constexpr bool kNL = NL;  // no light (shade NL)
-  static constexpr uint32_t kLdsMats = 16;
-  static constexpr int kStack = 0;
-  static constexpr int kLdsNodes = 0;
+struct WideTrav : TravDefaults {  // (no cold state in LDS: its LDS holds the tree and the stacks)
+  static constexpr bool kWide = true;
+  static constexpr bool kLL = LL, kNL = NL, kMoving = MOV;
   static constexpr int kWaves = sizeof(R) == 4 ? (LDSN ? RT_WIDE_WAVES : RT_WIDE_WAVES_GLOBAL)
                                                : (LDSN ? (NL ? RT_WIDE_WAVES_F64_NL : RT_WIDE_WAVES_F64)
                                                        : (LL ? RT_WIDE_WAVES_GLOBAL_F64_LL : RT_WIDE_WAVES_GLOBAL_F64));
-  static constexpr bool kFlat = false;
-  static constexpr bool kWide = true;
-  static constexpr bool kColdLds = false;  // its LDS holds the tree and the stacks
   // (Path LT) the fp64 LL kernel over a tree in HBM (C4): its throughput in LDS, 6 KB a block, for which its LDS stack
   // keeps 18 entries instead of 24: 339.2 -> 331.8 ms/frame, writes 16.4 -> 9.4 GB per launch (r06d). The fp64 NL
   // kernel over an LDS tree (C3) lost with it: 63.55 -> 68.08 ms/frame
   static constexpr bool kThrLds = sizeof(R) == 8 && !LDSN && LL;
-  static constexpr bool kTablesLds = false;
   static constexpr bool kLean = true;  // registers for the traversal (fewer spills)
   static constexpr bool kNoRad = true;
-  static constexpr bool kMoving = MOV;
   using StackT = WStackT<LDSN>;
   using WW = typename WWord<R>::T;
   // LDS layout: [nodes, kWNodeLdsStride each][primitive words][stack: entries x kBlock of StackT]
@@ -1220,8 +1069,32 @@ struct Lds<0> {
   uint32_t v[1];
 };
 
+// RT_SECTION_CLOCKS (development build, scripts/dev_sections.py): RT_LANE_TIMED(sum, expr) and RT_WAVE_TIMED(k, expr)
+// evaluate expr and add the shader-clock cycles it took to a lane's own sum, or -- by the first of the wave's lanes
+// that evaluate it -- to count k of the block's wave-level counts (rt_device.h wide_stats_lds). The product build
+// evaluates expr alone.
 #ifdef RT_SECTION_CLOCKS
 __device__ unsigned long long g_section_clocks[4];  // trace, shade, store, lanes
+struct LaneTimer {
+  uint64_t& sum;
+  uint64_t c0;
+  __device__ __forceinline__ explicit LaneTimer(uint64_t& s) : sum(s), c0(clock64()) {}
+  __device__ __forceinline__ ~LaneTimer() { sum += clock64() - c0; }
+};
+struct WaveTimer {
+  int k;
+  uint64_t c0;
+  __device__ __forceinline__ explicit WaveTimer(int k_) : k(k_), c0(clock64()) {}
+  __device__ __forceinline__ ~WaveTimer() {
+    if (__lane_id() == (uint32_t)__ffsll((unsigned long long)__ballot(1)) - 1)
+      atomicAdd(wide_stats_lds() + k, (unsigned long long)(clock64() - c0));
+  }
+};
+#define RT_LANE_TIMED(sum, ...) [&] { LaneTimer tm_(sum); return __VA_ARGS__; }()
+#define RT_WAVE_TIMED(k, ...) [&] { WaveTimer tm_(k); return __VA_ARGS__; }()
+#else
+#define RT_LANE_TIMED(sum, ...) (__VA_ARGS__)
+#define RT_WAVE_TIMED(k, ...) (__VA_ARGS__)
 #endif
 
 template <class R, class Trav, bool CAMX>
@@ -1246,38 +1119,23 @@ __device__ __forceinline__ void step_body(const Params<R>& p) {
     Path<R> s;
     load_path(p, slot, Dv, s);
 #ifdef RT_SECTION_CLOCKS
-    uint64_t c_trace = 0, c_shade = 0;
+    uint64_t c_trace = 0, c_shade = 0, c_store = 0;
 #endif
 #pragma unroll 1
     for (int k = 0; k < p.K; k++) {
       R t;
       uint32_t e, nm = 0;
       int32_t inst;
-#ifdef RT_SECTION_CLOCKS
-      const uint64_t c0 = clock64();
-#endif
-      Trav::run(p.sc, lds_nodes, s, Keys{s.ks}, stk.v + threadIdx.x, t, e, inst, nm);
+      RT_LANE_TIMED(c_trace, Trav::run(p.sc, lds_nodes, s, Keys{s.ks}, stk.v + threadIdx.x, t, e, inst, nm));
       segs++;
-#ifdef RT_SECTION_CLOCKS
-      const uint64_t c1 = clock64();
-      const bool more = shade<R, CAMX, Trav::kFlat>(p, s, t, e, inst, nm);
-      const uint64_t c2 = clock64();
-      c_trace += c1 - c0;
-      c_shade += c2 - c1;
-      if (!more) break;
-#else
-      if (!shade<R, CAMX, Trav::kFlat>(p, s, t, e, inst, nm)) break;
-#endif
+      if (!RT_LANE_TIMED(c_shade, shade<R, CAMX, ShadeGeneral<Trav::kFlat>>(p, s, t, e, inst, nm))) break;
     }
+    RT_LANE_TIMED(c_store, store_path(p, slot, s));
 #ifdef RT_SECTION_CLOCKS
-    const uint64_t c3 = clock64();
-#endif
-    store_path(p, slot, s);
-#ifdef RT_SECTION_CLOCKS
-    // development build: shader-clock cycles per section, summed over lanes (divide by the lane count)
+    // shader-clock cycles per section, summed over lanes (divide by the lane count)
     atomicAdd(&g_section_clocks[0], (unsigned long long)c_trace);
     atomicAdd(&g_section_clocks[1], (unsigned long long)c_shade);
-    atomicAdd(&g_section_clocks[2], (unsigned long long)(clock64() - c3));
+    atomicAdd(&g_section_clocks[2], (unsigned long long)c_store);
     atomicAdd(&g_section_clocks[3], 1ull);
 #endif
   }
@@ -1292,21 +1150,34 @@ __device__ __forceinline__ void step_body(const Params<R>& p) {
 }
 
 // Persistent form of the same loop (the default schedule): the grid is what the chip holds
-// resident, every lane keeps its path state in registers for the whole render. Dynamic
-// (persist 2): shade's path regeneration pulls the next item from the wave's queue, refilled a
-// batch at a time from the per-XCD heads (one returning atomic per 64 items; per-lane atomics on
-// one counter for the whole chip serialised across the 8 XCDs' L2s: measured 6x slower on C2).
-// Static (persist 1): lanes walk items lane, lane + P, ... (P = grid lanes). No state goes
-// through HBM between segments, there is no launch per K segments and no live-slot compaction.
-// Trav::Tables for the flat program, an empty stand-in for the others
-template <class R, class Trav, bool = Trav::kTablesLds>
-struct FlatTables {
-  struct T {};
-};
-template <class R, class Trav>
-struct FlatTables<R, Trav, true> {
-  using T = typename Trav::Tables;
-};
+// resident, every lane keeps its path state in registers for the whole render. shade's path
+// regeneration pulls the next item from the wave's queue, refilled a batch at a time from the
+// per-XCD heads (one returning atomic per 64 items; per-lane atomics on one counter for the whole
+// chip serialised across the 8 XCDs' L2s: measured 6x slower on C2). No state goes through HBM
+// between segments, there is no launch per K segments and no live-slot compaction.
+//
+// The kernel's parameters, read from the kernarg segment afresh each segment (the asm hides the
+// pointer from loop-invariant hoisting): hoisted, they outgrow the SGPR file and spill into VGPR
+// lanes, one v_readlane per use (C2 flat program: 73 SGPR spills -> 0, 24.9 -> 23.9 ms/frame;
+// scalar loads hit the constant cache. The wide kernels, with the lean path state: C3 fp32 51.9 ->
+// 51.1 ms/frame, fp64 71.3 -> 70.7, C4 neutral)
+template <class R>
+__device__ __forceinline__ const Params<R>& reload_params() {
+  using KP = const __attribute__((address_space(4))) Params<R>*;
+  KP kp = (KP)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(kp));
+  return *(const Params<R>*)kp;
+}
+// True (and the fault word set) once a lane has traced more segments than its cap, which cannot happen:
+// every segment advances a bounce-capped path
+template <class R>
+__device__ __forceinline__ bool seg_cap_hit(const Params<R>& q, uint64_t segs) {
+  if (segs > q.seg_cap) {
+    atomicOr(q.fault, 1u);
+    return true;
+  }
+  return false;
+}
 template <class R, class Trav, bool CAMX>
 __device__ __forceinline__ void persist_body(const Params<R>& p) {
   __shared__ Lds<Trav::kStack * kBlock> stk;
@@ -1328,30 +1199,32 @@ __device__ __forceinline__ void persist_body(const Params<R>& p) {
     wstk = Trav::fill(p.sc, dyn_lds) + threadIdx.x;
     trav_nodes = (const Node<R>*)dyn_lds;
   }
-  [[maybe_unused]] const typename FlatTables<R, Trav>::T* flat_tb = nullptr;
+  // shade's LDS tables (ShadeOf<Trav>::kMatsLds, kLL): the materials, and the LL kernels' (colour, kind) records
+  const Material<R>* mats = nullptr;
+  const R4<R>* lm = nullptr;
+  [[maybe_unused]] const typename Trav::Tables* flat_tb = nullptr;
   if constexpr (Trav::kTablesLds) {  // the host launches this kernel only when the tables fit
-    __shared__ typename FlatTables<R, Trav>::T tb;
+    __shared__ typename Trav::Tables tb;
     Trav::fill(p.sc, tb);
     __syncthreads();
     flat_tb = &tb;
+    mats = tb.m;
+    lm = tb.lm;
   }
   // the wide and linear LL kernels: the materials as (colour, kind) records in LDS, kind 0 lambertian, 1
   // diffuse_light, 2 isotropic (shade LL, LLI)
-  [[maybe_unused]] const R4<R>* wlm = nullptr;
-  if constexpr (Trav::kWide || Trav::kLinLL) {
-    if constexpr (Trav::kLL) {
-      __shared__ R4<R> wlm_tab[Trav::kLdsMats];
-      for (uint32_t j = threadIdx.x; j < p.sc.n_mats; j += kBlock) {
-        const Material<R>& m = p.sc.mats[j];
-        wlm_tab[j] = R4<R>{m.tx.c0[0], m.tx.c0[1], m.tx.c0[2],
-                           m.kind == M_DIFFUSE_LIGHT ? R(1) : (m.kind == M_ISOTROPIC ? R(2) : R(0))};
-      }
-      __syncthreads();
-      wlm = wlm_tab;
+  if constexpr (Trav::kLL && !Trav::kTablesLds) {  // (the flat program's table is in its Tables)
+    __shared__ R4<R> wlm_tab[Trav::kLdsMats];
+    for (uint32_t j = threadIdx.x; j < p.sc.n_mats; j += kBlock) {
+      const Material<R>& m = p.sc.mats[j];
+      wlm_tab[j] = R4<R>{m.tx.c0[0], m.tx.c0[1], m.tx.c0[2],
+                         m.kind == M_DIFFUSE_LIGHT ? R(1) : (m.kind == M_ISOTROPIC ? R(2) : R(0))};
     }
+    __syncthreads();
+    lm = wlm_tab;
   }
   uint32_t item0 = blockIdx.x * kBlock + threadIdx.x;
-  if (p.persist == 2) {
+  if (p.persist == kPersist) {
     if ((threadIdx.x & 63) == 0) {
       __hip_atomic_store(wave_queue(), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
       __hip_atomic_store(wave_queue() + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
@@ -1369,98 +1242,32 @@ __device__ __forceinline__ void persist_body(const Params<R>& p) {
       using StackT = typename Trav::StackT;
       const uint32_t root = Trav::root(p.sc);
       WideRayT<R> ry{root, 0, Num<R>::inf(), kNoHit, 1u};
-      using KP = const __attribute__((address_space(4))) Params<R>*;
-      const KP kp0 = (KP)__builtin_amdgcn_kernarg_segment_ptr();
 #pragma unroll 1
       for (;;) {
-        KP kp = kp0;
-        asm volatile("" : "+s"(kp));
-        const Params<R>& q = *(const Params<R>*)kp;
-#ifdef RT_SECTION_CLOCKS
-        const uint64_t c0 = clock64();
-        const bool fin = Trav::steps(q.sc, trav_nodes, s, (StackT*)wstk, ry);
-        if (__lane_id() == (uint32_t)__ffsll((unsigned long long)__ballot(1)) - 1)
-          atomicAdd(wide_stats_lds() + 6, (unsigned long long)(clock64() - c0));
-        if (!fin) continue;
-#else
-        if (!Trav::steps(q.sc, trav_nodes, s, (StackT*)wstk, ry)) continue;
-#endif
-        if (++segs > q.seg_cap) {  // cannot happen: every segment advances a bounce-capped path
-          atomicOr(q.fault, 1u);
-          break;
-        }
+        const Params<R>& q = reload_params<R>();
+        if (!RT_WAVE_TIMED(6, Trav::steps(q.sc, trav_nodes, s, (StackT*)wstk, ry))) continue;
+        if (seg_cap_hit(q, ++segs)) break;
         const R t = ry.tmax;
         const uint32_t e = ry.e;
         ry = WideRayT<R>{root, 0, Num<R>::inf(), kNoHit, 1u};
-#ifdef RT_SECTION_CLOCKS
         RT_WIDE_STAT(4);
-        const uint64_t c1 = clock64();
-        const bool more = shade<R, CAMX, false, Trav::kMoving, Trav::kLL, Trav::kLL, Trav::kNL>(q, s, t, e, -1, 0, nullptr, wlm);
-        if (__lane_id() == (uint32_t)__ffsll((unsigned long long)__ballot(1)) - 1)
-          atomicAdd(wide_stats_lds() + 7, (unsigned long long)(clock64() - c1));
-        if (!more) break;
-#else
-        if (!shade<R, CAMX, false, Trav::kMoving, Trav::kLL, Trav::kLL, Trav::kNL>(q, s, t, e, -1, 0, nullptr, wlm)) break;
-#endif
-      }
-    } else if constexpr (Trav::kTablesLds) {
-      // the flat program with its records and materials in LDS (Trav::Tables); the parameters are
-      // reloaded per segment as below
-      using KP = const __attribute__((address_space(4))) Params<R>*;
-      const KP kp0 = (KP)__builtin_amdgcn_kernarg_segment_ptr();
-#pragma unroll 1
-      for (;;) {
-        KP kp = kp0;
-        asm volatile("" : "+s"(kp));
-        const Params<R>& q = *(const Params<R>*)kp;
-        R t;
-        uint32_t e, nm = 0;
-        int32_t inst;
-        Trav::run_lds(q.sc, *flat_tb, s, t, e, inst, nm);
-        if (++segs > q.seg_cap) {  // cannot happen: every segment advances a bounce-capped path
-          atomicOr(q.fault, 1u);
-          break;
-        }
-        if (!shade<R, CAMX, true, true, true, Trav::kLL>(q, s, t, e, inst, nm, flat_tb->m, flat_tb->lm)) break;
+        if (!RT_WAVE_TIMED(7, shade<R, CAMX, ShadeOf<Trav>>(q, s, t, e, -1, 0, mats, lm))) break;
       }
     } else {
-      // The parameters are read from the kernarg segment afresh each segment (the asm hides
-      // the pointer from loop-invariant hoisting): hoisted, they outgrow the SGPR file and spill
-      // into VGPR lanes, one v_readlane per use (C2 flat program: 73 SGPR spills -> 0, 24.9 ->
-      // 23.9 ms/frame; scalar loads hit the constant cache)
-      using KP = const __attribute__((address_space(4))) Params<R>*;
-      const KP kp0 = (KP)__builtin_amdgcn_kernarg_segment_ptr();
+      // the flat program with its records and materials in LDS (Trav::Tables), or the scene in global memory
 #pragma unroll 1
       for (;;) {
-        KP kp = kp0;
-        asm volatile("" : "+s"(kp));
-        const Params<R>& q = *(const Params<R>*)kp;
+        const Params<R>& q = reload_params<R>();
         R t;
         uint32_t e, nm = 0;
         int32_t inst;
-#ifdef RT_SECTION_CLOCKS
         RT_WIDE_STAT(0);
-        const uint64_t c0 = clock64();
-#endif
-        Trav::run(q.sc, trav_nodes, s, Keys{s.ks}, stk_lane, t, e, inst, nm);
-        if (++segs > q.seg_cap) {  // cannot happen: every segment advances a bounce-capped path
-          atomicOr(q.fault, 1u);
-          break;
-        }
-#ifdef RT_SECTION_CLOCKS
-        const uint64_t c1 = clock64();
-        const bool more = shade<R, CAMX, Trav::kFlat, true, Trav::kLinLL, Trav::kLinLL, false, Trav::kLinLL>(
-            q, s, t, e, inst, nm, nullptr, wlm);
-        if (__lane_id() == (uint32_t)__ffsll((unsigned long long)__ballot(1)) - 1) {
-          atomicAdd(wide_stats_lds() + 6, (unsigned long long)(c1 - c0));
-          atomicAdd(wide_stats_lds() + 7, (unsigned long long)(clock64() - c1));
-        }
-        if (!more) break;
-#else
-        if (!shade<R, CAMX, Trav::kFlat, true, Trav::kLinLL, Trav::kLinLL, false, Trav::kLinLL>(q, s, t, e, inst, nm,
-                                                                                            nullptr, wlm))
-          break;
-#endif
+        if constexpr (Trav::kTablesLds)
+          RT_WAVE_TIMED(6, Trav::run_lds(q.sc, *flat_tb, s, t, e, inst, nm));
+        else
+          RT_WAVE_TIMED(6, Trav::run(q.sc, trav_nodes, s, Keys{s.ks}, stk_lane, t, e, inst, nm));
+        if (seg_cap_hit(q, ++segs)) break;
+        if (!RT_WAVE_TIMED(7, shade<R, CAMX, ShadeOf<Trav>>(q, s, t, e, inst, nm, mats, lm))) break;
       }
     }
   }
@@ -1577,7 +1384,7 @@ __global__ __launch_bounds__(kBlock) void k_compact(const void* Dp, int prec, co
 }
 
 // ------------------------------------------------------------------ resolve (camera.h:169-170)
-// A render in passes (render()): pass k adds its chunks to the running sums that the earlier passes left in
+// A render in passes (rt_plan.h ItemPlan): pass k adds its chunks to the running sums that the earlier passes left in
 // `out` (first: from 0), in chunk order, and the last pass divides -- the same additions in the same order as
 // one pass over every chunk, so the image does not depend on the pass split.
 template <class R>
@@ -1631,216 +1438,7 @@ __global__ __launch_bounds__(kBlock) void k_pixmap(const uint4* tl, uint32_t nti
   pixmap[i] = (t.x + x) | (t.y + y) << 16;
 }
 
-// camera.h:137-141, 246, 253, 278-279 evaluated in double exactly as the reference orders them
-CamDev make_view(const rt_camera_desc* c) {
-  CamDev v{};
-  v.mode = c->mode;
-  double du[3], dv[3], dir00[3], pos00[3];
-  for (int k = 0; k < 3; k++) {
-    du[k] = (c->right[k] * c->viewport_width) / (double)c->image_width;
-    dv[k] = (c->up[k] * -c->viewport_height) / (double)c->image_height;
-  }
-  for (int k = 0; k < 3; k++) {
-    double a = c->dir[k] * c->focal_length;
-    double b = c->right[k] * (c->viewport_width / 2.0);
-    double u = c->up[k] * (c->viewport_height / 2.0);
-    double e = (du[k] + dv[k]) * 0.5;
-    dir00[k] = ((a - b) + u) + e;
-    pos00[k] = ((c->pos[k] - b) + u) + e;
-  }
-  v.pos = {c->pos[0], c->pos[1], c->pos[2]};
-  v.du = {du[0], du[1], du[2]};
-  v.dv = {dv[0], dv[1], dv[2]};
-  v.dir00 = {dir00[0], dir00[1], dir00[2]};
-  v.pos00 = {pos00[0], pos00[1], pos00[2]};
-  v.dir = {c->dir[0], c->dir[1], c->dir[2]};
-  v.fdir = {c->focus_dist * c->dir[0], c->focus_dist * c->dir[1], c->focus_dist * c->dir[2]};
-  v.disk_u = {c->defocus_u[0], c->defocus_u[1], c->defocus_u[2]};
-  v.disk_v = {c->defocus_v[0], c->defocus_v[1], c->defocus_v[2]};
-  v.focal = c->focal_length;
-  return v;
-}
-
-template <class R>
-V<R> tov(const double* a) {
-  return {(R)a[0], (R)a[1], (R)a[2]};
-}
-
-}  // namespace
-
-// ====================================================================== host side
-
-struct DevBuf {
-  void* ptr = nullptr;
-  size_t bytes = 0;
-};
-
-struct rt_context {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  std::string err;
-  CompiledScene scene;
-  bool has_scene = false;
-  DevBuf scene32, scene64;
-  DevBuf state, partial, pixmap, queue0, queue1, blk, out_tmp, counters, camx, heads, tiles;
-  DevBuf wide_spill;  // the wide traversal's stack entries past wide_lds_stack (deep trees in HBM)
-  CamDev cam_host;  // source of camx (kept alive for the async copy)
-  uint32_t* total_host = nullptr;  // pinned: [0] live slots, [1] fault word, [16..] segment counter shards
-  uint64_t samples = 0;
-  rt_counters last{};  // host-known totals since rt_reset_counters; segments and step_ms settle in settle()
-  int timing = 0;
-  std::vector<hipEvent_t> events;
-  // asynchronous renders (device output): what rt_stats / rt_reset_counters / a host-output render
-  // settle with one sync -- the stream, the timing events recorded since the last settle
-  hipStream_t pend_stream = nullptr;
-  bool pending = false;
-  size_t ev_used = 0;
-  DevBuf fault;  // sticky internal-error word of the persistent kernel (zeroed by rt_reset_counters)
-  // inputs kept on the device while they do not change between calls
-  std::vector<uint4> tiles_dev;  // the tile list k_pixmap last expanded into pixmap
-  void* pixmap_for = nullptr;    // pixmap buffer that expansion went to
-  uint32_t pixmap_npix = 0;      // pixels it expanded: a tile entry {x0, y0, width, first} does not
-                                 // hold the height, so the last tile can change with the list equal
-  CamDev cam_dev{};              // the camera view in camx
-  bool cam_valid = false;
-  // the compiled scene is copied into scene32 / scene64 by the first render after rt_scene_upload,
-  // on that render's stream: a copy made on another stream is not guaranteed visible to the kernels
-  // of the render stream (their launch need not invalidate the L2 lines of the previous scene)
-  bool scene_dirty32 = false, scene_dirty64 = false;
-};
-
-namespace {
-
-std::mutex g_err_mu;
-std::string g_create_err;
-
-rt_status set_err(rt_context* c, rt_status s, const std::string& m) {
-  if (c) {
-    c->err = m;
-  } else {
-    std::lock_guard<std::mutex> lk(g_err_mu);
-    g_create_err = m;
-  }
-  return s;
-}
-
-#define RT_HIP(ctx, call)                                                                   \
-  do {                                                                                      \
-    hipError_t e_ = (call);                                                                 \
-    if (e_ != hipSuccess)                                                                   \
-      return set_err((ctx), RT_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
-  } while (0)
-
-// Grow a context buffer. The only work that can still read the old buffer is this context's
-// outstanding device-output render (host-output renders return finished, and a render on another
-// stream waits for pend_stream first): wait for that stream, not for the whole device.
-rt_status ensure(rt_context* c, DevBuf& b, size_t bytes) {
-  if (b.ptr && b.bytes >= bytes) return RT_OK;
-  if (b.ptr) {
-    if (c->pending) RT_HIP(c, hipStreamSynchronize(c->pend_stream));
-    RT_HIP(c, hipFree(b.ptr));
-    b.ptr = nullptr;
-    b.bytes = 0;
-  }
-  size_t want = std::max<size_t>(bytes, 256);
-  hipError_t e = hipMalloc(&b.ptr, want);
-  if (e != hipSuccess) {
-    b.ptr = nullptr;
-    (void)hipGetLastError();
-    return set_err(c, RT_ERR_OUT_OF_MEMORY,
-                   "hipMalloc(" + std::to_string(want) + " bytes): " + hipGetErrorString(e));
-  }
-  b.bytes = want;
-  return RT_OK;
-}
-
-hipEvent_t take_event(rt_context* c, size_t idx) {
-  while (c->events.size() <= idx) {
-    hipEvent_t e = nullptr;
-    if (hipEventCreate(&e) != hipSuccess) return nullptr;
-    c->events.push_back(e);
-  }
-  return c->events[idx];
-}
-
-// Wait for the context's outstanding renders and fold their device-side results into c->last:
-// the cumulative segment count, the kernel time of the timing events, the fault word.
-rt_status settle(rt_context* c) {
-  if (!c->pending) return RT_OK;
-  c->pending = false;
-  RT_HIP(c, hipStreamSynchronize(c->pend_stream));
-  unsigned long long* shards = (unsigned long long*)(c->total_host + 16);
-  RT_HIP(c, hipMemcpy(shards, c->counters.ptr, sizeof(unsigned long long) * kSegShards, hipMemcpyDeviceToHost));
-  uint64_t segs = 0;
-  for (int k = 0; k < kSegShards; k++) segs += shards[k];
-  c->last.segments = segs;
-  double ms = 0;
-  for (size_t k = 0; k + 1 < c->ev_used; k += 2) {
-    float a = 0;
-    RT_HIP(c, hipEventElapsedTime(&a, c->events[k], c->events[k + 1]));
-    ms += a;
-  }
-  c->ev_used = 0;
-  c->last.step_ms += ms;
-  uint32_t fault = 0;
-  if (c->fault.ptr) RT_HIP(c, hipMemcpy(&fault, c->fault.ptr, 4, hipMemcpyDeviceToHost));
-  if (fault) return set_err(c, RT_ERR_HIP, "a path did not finish (internal error)");
-  return RT_OK;
-}
-
-// Division by a launch constant d >= 1 as a multiply (Granlund-Montgomery): with
-// k = 32 + ceil(log2 d) and m = floor(2^k / d) + 1, (n * m) >> k == n / d for every n < 2^31
-// (m d - 2^k <= d, so the error n (m d - 2^k) / 2^k stays below 1/d; n m < 2^64).
-void div_magic(uint32_t d, uint64_t& m, uint32_t& k) {
-  uint32_t l = 0;
-  while ((1ull << l) < d) l++;
-  k = 32 + l;
-  m = (uint64_t)((((unsigned __int128)1) << k) / d) + 1;
-}
-
-template <class R>
-DevScene<R> dev_scene(const SceneHeader& h, void* base) {
-  auto at = [&](uint64_t off) { return (const unsigned char*)base + off; };
-  DevScene<R> s{};
-  s.quads = (const Quad<R>*)at(h.off_quads);
-  s.spheres = (const Sphere<R>*)at(h.off_spheres);
-  s.tris = (const Tri<R>*)at(h.off_tris);
-  s.insts = (const Instance<R>*)at(h.off_instances);
-  s.vols = (const Volume<R>*)at(h.off_volumes);
-  s.nodes = (const Node<R>*)at(h.off_nodes);
-  s.refs = (const uint32_t*)at(h.off_refs);
-  s.mats = (const Material<R>*)at(h.off_mats);
-  s.texs = (const Texture<R>*)at(h.off_texs);
-  s.light = (const Light<R>*)at(h.off_light);
-  s.lin = (const LinRec<R>*)at(h.off_linear);
-  s.n_linear = h.n_linear;
-  s.has_flat = (int32_t)h.has_flat;
-  s.flatq = (const FlatQuadT<R>*)at(h.off_flat_quad);
-  s.flatb = (const FlatBoxT<R>*)at(h.off_flat_box);
-  for (int a = 0; a < 3; a++) s.n_flatq[a] = h.n_flat_quad[a];
-  s.n_flatb = h.n_flat_box;
-  s.n_mats = h.n_mats;
-  s.root = h.root;
-  s.background = h.background;
-  s.has_volumes = h.has_volumes;
-  s.n_nodes = h.n_nodes;
-  s.texdata = (const double*)at(h.off_texdata);
-  s.images = (const uint8_t*)at(h.off_images);
-  s.has_procedural = h.n_texdata > 0 || h.has_cell_noise;
-  s.has_wide = (int32_t)h.has_wide;
-  s.wnodes = (const WNode*)at(h.off_wnodes);
-  s.wprims = (const typename WWord<R>::T*)at(h.off_wprims);
-  s.n_wnodes = h.n_wnodes;
-  s.n_wprim_words = h.n_wprim_words;
-  s.wroot = h.wroot;
-  s.wide_stack = h.wide_stack;
-  s.wide_kinds = h.wide_kinds;
-  s.wide_big = h.wide_big;
-  s.wide_top = h.wide_top;
-  s.wnodesh = h.has_wnodesh ? (const WNodeH*)at(h.off_wnodesh) : nullptr;
-  s.quads64 = h.has_quads64 ? (const Quad<double>*)at(h.off_quads64) : nullptr;
-  return s;
-}
+// ====================================================================== launch selection
 
 // Resident blocks of one kernel on one device (occupancy query x CU count), cached per (kernel,
 // device): every persistent kernel has its own register budget, so one kernel's grid must not
@@ -1866,17 +1464,14 @@ thread_local uint64_t t_grid_lanes = 0;
 
 template <class KernelT, class R>
 void launch_one(KernelT kern, Params<R> p, uint32_t grid, hipStream_t st, size_t lds = 0) {
-  if (p.persist == 2) {  // as many blocks as the chip holds resident; lanes pull items
+  if (p.persist) {  // as many blocks as the chip holds resident; lanes pull items
     int dev = 0;
     const uint32_t res = hipGetDevice(&dev) == hipSuccess ? resident_blocks((const void*)kern, dev, lds) : 0;
     if (res > 0) grid = std::min<uint32_t>(grid, res);
     p.P = grid * kBlock;
     p.seg_cap = (uint64_t)p.n_items * p.chunk * (uint64_t)p.max_depth + 1;
-  } else if (p.persist) {  // the lanes stride over the items by the grid's lane count
-    p.P = grid * kBlock;
-    p.seg_cap = ((uint64_t)p.n_items + p.P - 1) / p.P * p.chunk * (uint64_t)p.max_depth + 1;
+    t_grid_lanes = (uint64_t)grid * kBlock;
   }
-  if (p.persist) t_grid_lanes = (uint64_t)grid * kBlock;
   hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), lds, st, p);
 }
 
@@ -1967,60 +1562,15 @@ void launch_k(const Params<R>& p, uint32_t grid, hipStream_t st) {
   }
 }
 
-// The kernel family a render takes, decided on the host from the compiled scene, the camera model, the
-// schedule and the traversal order (launch_step launches it).
-enum KernelFamily { KF_FLAT, KF_LIN_QUAD, KF_LIN_VOL, KF_LIN_SPH, KF_LIN_ALL, KF_WIDE, KF_STACK };
-KernelFamily kernel_family(const SceneHeader& h, int32_t cam_mode, bool persist, bool ordered) {
-  const bool persp = cam_mode == RT_CAM_PERSPECTIVE, procedural = h.n_texdata > 0 || h.has_cell_noise;
-  const bool sph = h.n_spheres > 0, tri = h.n_tris > 0, vol = h.has_volumes != 0;
-  // the flat program (world-space quads and boxes, fp32 and fp64); the extended kernels keep the linear one
-  if (!ordered && h.has_flat && persp && !procedural) return KF_FLAT;
-  if (h.n_linear > 0) {
-    if (!sph && !tri) return vol ? KF_LIN_VOL : KF_LIN_QUAD;
-    return (sph && !tri && !vol) ? KF_LIN_SPH : KF_LIN_ALL;
-  }
-  // the wide BVH (persistent schedule, base kernels; fp64 rays since round 3)
-  if (!ordered && h.has_wide && persist && persp && !procedural) return KF_WIDE;
-  return KF_STACK;
-}
-const char* family_name(KernelFamily f) {
-  static const char* n[] = {"flat program", "linear program (quads)", "linear program (quads + volumes)",
-                            "linear program (spheres)", "linear program (all kinds)", "wide BVH", "binary BVH"};
-  return n[f];
-}
-// RT_DEV_ONLY (development builds for register/spill iteration, scripts/kernel_usage.py): instantiate one
-// kernel family only -- 1 the flat program, 2 the wide BVH, 3 the quad + volume linear program. 0:
-// everything. A render (and rt_scene_check) that needs a family such a build omits fails with
-// RT_ERR_UNSUPPORTED instead of launching nothing.
-#ifndef RT_DEV_ONLY
-#define RT_DEV_ONLY 0
-#endif
-constexpr bool family_built(KernelFamily f) {
-  return RT_DEV_ONLY == 0 || (RT_DEV_ONLY == 1 && f == KF_FLAT) || (RT_DEV_ONLY == 2 && f == KF_WIDE) ||
-         (RT_DEV_ONLY == 3 && f == KF_LIN_VOL);
-}
-// a lambertian + diffuse_light scene with solid textures (a background too) and an axis-aligned quad light (the
-// Cornell configs): the flat kernel's LL form (shade LL)
-bool lamb_light_scene(const SceneHeader& h) {
-  const uint32_t ok_m = (1u << M_LAMBERTIAN) | (1u << M_DIFFUSE_LIGHT);
-  return (h.mat_kinds & ~ok_m) == 0 && (h.tex_kinds & ~(1u << T_SOLID)) == 0 && h.light_kind == L_QUAD &&
-         h.light_aligned != 0;
-}
-// no light, lambertian / metal / dielectric materials with solid or checker textures (RTOW): shade NL
-bool no_light_scene(const SceneHeader& h) {
-  const uint32_t ok_m = (1u << M_LAMBERTIAN) | (1u << M_METAL) | (1u << M_DIELECTRIC);
-  return (h.mat_kinds & ~ok_m) == 0 && (h.tex_kinds & ~((1u << T_SOLID) | (1u << T_CHECKER))) == 0 &&
-         h.light_kind == L_NONE;
-}
-// lambertian, isotropic and diffuse_light materials with solid textures and an axis-aligned quad light (C5)
-bool lamb_iso_light_scene(const SceneHeader& h) {
-  const uint32_t ok_m = (1u << M_LAMBERTIAN) | (1u << M_DIFFUSE_LIGHT) | (1u << M_ISOTROPIC);
-  return (h.mat_kinds & ~ok_m) == 0 && (h.tex_kinds & ~(1u << T_SOLID)) == 0 && h.light_kind == L_QUAD &&
-         h.light_aligned != 0;
-}
+}  // namespace
+
+// ====================================================================== rt_launch.h
+namespace rtd {
+
 template <class R>
-void launch_step(const Params<R>& p, KernelFamily fam, bool ll, bool nl, bool lli, int stack, uint32_t grid,
+void launch_step(const LaunchParams<R>& lp, KernelFamily fam, bool ll, bool nl, bool lli, int stack, uint32_t grid,
                  hipStream_t st) {
+  const Params<R> p{lp};
   switch (fam) {
     case KF_FLAT:
       if constexpr (family_built(KF_FLAT)) {
@@ -2076,327 +1626,52 @@ void launch_step(const Params<R>& p, KernelFamily fam, bool ll, bool nl, bool ll
   }
 }
 
+uint64_t last_grid_lanes() { return t_grid_lanes; }
+
 template <class R>
-rt_status render(rt_context* c, const rt_camera_desc* cam, const rt_render_params* prm, const rt_tile* tiles,
-                 int32_t ntiles, void* out, int32_t out_dev, hipStream_t st) {
-  const bool f64 = sizeof(R) == 8;
-  const CompiledScene& cs = c->scene;
-  const SceneHeader& hdr = f64 ? cs.hdr64 : cs.hdr;
-  void* sbase = f64 ? c->scene64.ptr : c->scene32.ptr;
-  bool& dirty = f64 ? c->scene_dirty64 : c->scene_dirty32;
-  auto t0 = std::chrono::steady_clock::now();
-  // A device-output render still pending on another stream reads the context's shared buffers
-  // (pixmap, tiles, camx, heads, partial): wait for it before this call writes any of them.
-  if (c->pending && c->pend_stream != st) RT_HIP(c, hipStreamSynchronize(c->pend_stream));
-  if (dirty) {  // the scene uploaded since the last render of this precision, stream-ordered before its kernels
-    const std::vector<unsigned char>& blob = f64 ? cs.blob64 : cs.blob32;
-    RT_HIP(c, hipMemcpyAsync(sbase, blob.data(), blob.size(), hipMemcpyHostToDevice, st));
-    dirty = false;
-    // outstanding from here on, whatever this call does next (an empty tile list or max_depth <= 0
-    // launches nothing that reads the scene): a later render on another stream waits for st
-    c->pending = true;
-    c->pend_stream = st;
-  }
-
-  // pixel map: tiles packed in order, row-major inside each tile (expanded by k_pixmap)
-  std::vector<uint4> tl;
-  tl.reserve(ntiles);
-  uint64_t npix64 = 0;
-  for (int t = 0; t < ntiles; t++) {
-    if (tiles[t].width == 0 || tiles[t].height == 0) continue;
-    tl.push_back(make_uint4((uint32_t)tiles[t].x0, (uint32_t)tiles[t].y0, (uint32_t)tiles[t].width, (uint32_t)npix64));
-    npix64 += (uint64_t)tiles[t].width * (uint64_t)tiles[t].height;
-  }
-  if (npix64 >= (1ull << 31)) return set_err(c, RT_ERR_INVALID_ARGUMENT, "too many pixels in one call");
-  const uint32_t npix = (uint32_t)npix64;
-  if (npix == 0) return RT_OK;
-  const size_t out_elems = 3ull * npix;
-  rt_status s;
-  void* dout = out;
-  if (!out_dev) {
-    if ((s = ensure(c, c->out_tmp, out_elems * sizeof(R))) != RT_OK) return s;
-    dout = c->out_tmp.ptr;
-  }
-
-  if (prm->max_depth <= 0) {  // ray_color(r, 0) is black for every sample (camera.h:194-195)
-    hipLaunchKernelGGL(k_zero<R>, dim3((unsigned)((out_elems + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
-                       (R*)dout, (uint64_t)out_elems);
-  } else {
-    const uint32_t spp = (uint32_t)prm->spp;
-    // the flat program's items are cheaper per sample, so its default items are twice as long
-    // (fewer item ends, dequeues and partial-sum stores; C2: 23.9 -> 23.5 ms/frame)
-    const bool flat_prog = hdr.has_flat && prm->traversal != RT_TRAV_ORDERED &&
-                           make_view(cam).mode == RT_CAM_PERSPECTIVE && !(hdr.n_texdata > 0 || hdr.has_cell_noise);
-    uint32_t chunk0 = prm->samples_per_item > 0 ? std::min<uint32_t>((uint32_t)prm->samples_per_item, spp)
-                                               : std::min<uint32_t>(auto_chunk(flat_prog), spp);
-    // a small frame (C1: 160,000 px x 64 spp is ~2 items of 16 per resident lane) takes smaller items, so
-    // the lanes that finish early find work while the last items run: the automatic size is halved until
-    // the whole frame has kItemsTarget items (the full image's pixels, not this call's tiles: the layout,
-    // and so the image, is the same for any tiling or rank count)
-    if (prm->samples_per_item <= 0) {
-      const uint64_t target = env_u32("RT_ITEMS_TARGET", kItemsTarget);
-      const uint64_t full = (uint64_t)cam->image_width * (uint64_t)cam->image_height;
-      while (chunk0 > kMinAutoChunk && full * ((spp + chunk0 - 1) / chunk0) < target) chunk0 /= 2;
-    }
-    // The frame's last items are short (auto item size only): a lane that takes a long item just
-    // before the queue runs dry keeps its wave resident while the others idle, and a small frame
-    // (one rank of eight) has few items per lane. The last tail_samples of every pixel come in
-    // items of tail_chunk samples; both depend on spp alone, so the image is the same for any
-    // tiling or rank count.
-    uint32_t chunk = chunk0, tail_chunk = chunk0, k_bulk = (spp + chunk0 - 1) / chunk0, nchunks = k_bulk;
-    if (prm->samples_per_item <= 0) {  // (fp64 too since round 3: round 2 kept uniform items of 16 for it)
-      const uint32_t ts = std::min<uint32_t>(spp, (uint32_t)((double)spp * auto_tail_frac(flat_prog) + 0.5));
-      tail_chunk = std::min(chunk, auto_tail_chunk(flat_prog));
-      for (;;) {
-        k_bulk = (spp - ts) / chunk;  // bulk items cover [0, k_bulk * chunk)
-        nchunks = k_bulk + (spp - k_bulk * chunk + tail_chunk - 1) / tail_chunk;
-        if (nchunks <= kMaxItemsPerPixel || chunk >= spp) break;
-        chunk = std::min(spp, 2 * chunk);
-        tail_chunk = std::min(chunk, 2 * tail_chunk);
-      }
-    }
-    // Passes: the item partial sums of a call are 3 R per (pixel, chunk) -- C5 fp64 (3840 x 2160 at 4096 spp,
-    // 192 chunks) would need 38 GB. The chunks come in passes of `cpp` chunks whose partial sums fit
-    // kPartialBudget (and whose items fit 32 bits); every pass is one launch, and its resolve adds its chunks
-    // to the running per-pixel sums in chunk order (k_resolve), so the image is the same for any split.
-    const uint64_t budget = (uint64_t)env_f64("RT_PARTIAL_BUDGET", (double)kPartialBudget);
-    const uint64_t per_chunk = 3ull * sizeof(R) * npix;
-    const uint32_t cpp = (uint32_t)std::max<uint64_t>(
-        1, std::min<uint64_t>({(uint64_t)nchunks, budget / per_chunk, ((1ull << 31) - 1) / npix}));
-    const uint32_t n_items = npix * cpp;  // items of the largest pass
-    // the default schedule is persistent (k_persist); an explicit segments_per_launch selects the
-    // launch-per-K-segments wavefront with HBM path state and live-slot compaction
-    const bool persist = prm->segments_per_launch <= 0;
-    const KernelFamily fam = kernel_family(hdr, cam->mode, persist, prm->traversal == RT_TRAV_ORDERED);
-    if (!family_built(fam))
-      return set_err(c, RT_ERR_UNSUPPORTED, std::string("this build (RT_DEV_ONLY) has no ") + family_name(fam) + " kernels");
-    const bool ll = lamb_light_scene(hdr), nl = no_light_scene(hdr), lli = lamb_iso_light_scene(hdr);
-    uint32_t P = prm->pool_slots > 0 ? (uint32_t)prm->pool_slots
-                 : persist       ? kAutoPersistLanes
-                                 : (f64 ? kAutoPool64 : kAutoPool32);
-    P = std::max<uint32_t>(1, std::min(P, n_items));
-    const uint32_t nblk_max = (P + kBlock - 1) / kBlock;
-
-    // path state: 5 R4 arrays (O, D, T, L, A) + uint4 keys (S) + uint4 exclusion/pixel (X), each P long
-    auto al = [](size_t x) { return (x + 255) & ~size_t(255); };
-    const size_t r4 = al(sizeof(R4<R>) * (size_t)P), sb = al(16 * (size_t)P), xb = al(16 * (size_t)P);
-    if (!persist) {
-      if ((s = ensure(c, c->state, 5 * r4 + sb + xb)) != RT_OK) return s;
-      if ((s = ensure(c, c->queue0, 4ull * P)) != RT_OK) return s;
-      if ((s = ensure(c, c->queue1, 4ull * P)) != RT_OK) return s;
-    }
-    if ((s = ensure(c, c->partial, 3ull * n_items * sizeof(R))) != RT_OK) return s;
-    c->last.passes += (nchunks + cpp - 1) / cpp;
-    c->last.partial_bytes = 3ull * n_items * sizeof(R);
-    const size_t pixmap_bytes = c->pixmap.bytes;
-    if ((s = ensure(c, c->pixmap, 4ull * npix)) != RT_OK) return s;
-    if (c->pixmap.bytes != pixmap_bytes) c->tiles_dev.clear();  // reallocated: the old map is gone
-    if ((s = ensure(c, c->blk, 4ull * (nblk_max + 2))) != RT_OK) return s;
-    const bool same_tiles = c->pixmap_for == c->pixmap.ptr && c->pixmap_npix == npix && c->tiles_dev.size() == tl.size() &&
-                            std::memcmp(c->tiles_dev.data(), tl.data(), sizeof(uint4) * tl.size()) == 0;
-    if (!same_tiles) {  // the pixel map of an unchanged tile list is still in pixmap
-      if ((s = ensure(c, c->tiles, sizeof(uint4) * tl.size())) != RT_OK) return s;
-      c->tiles_dev = tl;  // the copy's source outlives this call
-      c->pixmap_for = c->pixmap.ptr;
-      c->pixmap_npix = npix;
-      RT_HIP(c, hipMemcpyAsync(c->tiles.ptr, c->tiles_dev.data(), sizeof(uint4) * tl.size(), hipMemcpyHostToDevice,
-                               st));
-      hipLaunchKernelGGL(k_pixmap, dim3((npix + kBlock - 1) / kBlock), dim3(kBlock), 0, st,
-                         (const uint4*)c->tiles.ptr, (uint32_t)tl.size(), npix, (uint32_t*)c->pixmap.ptr);
-    }
-
-    unsigned char* sp = (unsigned char*)c->state.ptr;
-    Params<R> p{};
-    p.sc = dev_scene<R>(hdr, sbase);
-    const uint32_t wide_need = hdr.wide_stack;
-    constexpr uint32_t kWideLdsStack = wide_lds_stack<R>();
-    if (hdr.has_wide && wide_need > kWideLdsStack) {
-      // a deep wide tree: a spill area of (need - kWideLdsStack) entries for every lane the chip can hold
-      int ncu = 0;
-      RT_HIP(c, hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->device));
-      const uint32_t lanes = (uint32_t)std::max(ncu, 1) * 2048u;  // 32 waves of 64 per CU at most
-      if ((s = ensure(c, c->wide_spill, 4ull * (wide_need - kWideLdsStack) * lanes)) != RT_OK) return s;
-      p.sc.wide_spill = (uint32_t*)c->wide_spill.ptr;
-      p.sc.spill_lanes = lanes;
-    }
-    if (prm->traversal == RT_TRAV_ORDERED) p.sc.has_flat = p.sc.has_wide = 0;
-    p.sc.cam64 = nullptr;  // set with the camera below (perspective only)
-    p.O = (R4<R>*)sp;
-    p.D = (R4<R>*)(sp + r4);
-    p.T = (R4<R>*)(sp + 2 * r4);
-    p.L = (R4<R>*)(sp + 3 * r4);
-    p.A = (R4<R>*)(sp + 4 * r4);
-    p.S = (uint4*)(sp + 5 * r4);
-    p.X = (uint4*)(sp + 5 * r4 + sb);
-    p.partial = (R*)c->partial.ptr;
-    p.pixmap = (const uint32_t*)c->pixmap.ptr;
-    p.queue = nullptr;
-    p.n = P;
-    p.P = P;
-    p.npix = npix;
-    div_magic(npix, p.npix_m, p.npix_k);
-    p.n_items = n_items;
-    p.chunk = chunk;
-    p.k_bulk = k_bulk;
-    p.tail_chunk = tail_chunk;
-    p.spp = spp;
-    p.first_sample = (uint32_t)std::max(0, prm->first_sample);
-    p.W = (uint32_t)cam->image_width;
-    p.max_depth = prm->max_depth;
-    p.seed = prm->seed;
-    c->cam_host = make_view(cam);
-    if ((s = ensure(c, c->camx, sizeof(CamDev))) != RT_OK) return s;
-    if (!c->cam_valid || std::memcmp(&c->cam_dev, &c->cam_host, sizeof(CamDev)) != 0) {
-      RT_HIP(c, hipMemcpyAsync(c->camx.ptr, &c->cam_host, sizeof(CamDev), hipMemcpyHostToDevice, st));
-      c->cam_dev = c->cam_host;
-      c->cam_valid = true;
-    }
-    p.cam_mode = c->cam_host.mode;
-    p.camx = (const CamDev*)c->camx.ptr;
-    if (p.cam_mode == RT_CAM_PERSPECTIVE) p.sc.cam64 = p.camx;
-    p.seg_shards = (unsigned long long*)c->counters.ptr;
-    const int K = prm->segments_per_launch > 0 ? std::min(prm->segments_per_launch, 64) : kAutoSegments;
-    p.K = K;
-    uint64_t launches = 0, iters = 0;
-    size_t ev = 0;
-    if (c->timing && c->ev_used > 4096 && (s = settle(c)) != RT_OK) return s;  // bound the pending events
-    const size_t ev0 = c->ev_used;
-    if (persist) {
-      if ((s = ensure(c, c->fault, 4)) != RT_OK) return s;
-      p.persist = RT_PERSIST_MODE;
-      p.fault = (uint32_t*)c->fault.ptr;
-      if ((s = ensure(c, c->heads, 4ull * kHeads * kHeadStride)) != RT_OK) return s;
-      p.heads = (uint32_t*)c->heads.ptr;
-    }
-    for (uint32_t c0 = 0; c0 < nchunks; c0 += cpp) {  // the passes (one for every BASELINE config but C5)
-      const uint32_t pc = std::min(cpp, nchunks - c0);
-      p.chunk0 = c0;
-      p.n_items = npix * pc;
-      if (persist) {
-        // one launch of P lanes (pool_slots, or kAutoPersistLanes)
-        RT_HIP(c, hipMemsetAsync(c->heads.ptr, 0, 4ull * kHeads * kHeadStride, st));
-        const uint32_t grid = nblk_max;
-        if (c->timing) {
-          hipEvent_t e0 = take_event(c, ev0 + ev), e1 = take_event(c, ev0 + ev + 1);
-          if (!e0 || !e1) return set_err(c, RT_ERR_HIP, "hipEventCreate failed");
-          RT_HIP(c, hipEventRecord(e0, st));
-          launch_step<R>(p, fam, ll, nl, lli, cs.stack_need, grid, st);
-          RT_HIP(c, hipEventRecord(e1, st));
-          ev += 2;
-        } else {
-          launch_step<R>(p, fam, ll, nl, lli, cs.stack_need, grid, st);
-        }
-        RT_HIP(c, hipGetLastError());
-        c->last.grid_lanes = t_grid_lanes;
-        launches++;
-        iters++;
-        // a fault is reported by the settle after this call (rt_stats, or a host-output render)
-      } else {
-        p.queue = nullptr;
-        p.n = P;
-        if (p.cam_mode != RT_CAM_PERSPECTIVE || p.sc.has_procedural)
-          hipLaunchKernelGGL((k_init<R, true>), dim3(nblk_max), dim3(kBlock), 0, st, p);
-        else
-          hipLaunchKernelGGL((k_init<R, false>), dim3(nblk_max), dim3(kBlock), 0, st, p);
-        launches++;
-        uint32_t* qbuf[2] = {(uint32_t*)c->queue0.ptr, (uint32_t*)c->queue1.ptr};
-        int qsel = 0;
-        uint32_t* blk = (uint32_t*)c->blk.ptr;
-        uint32_t* d_total = blk + nblk_max + 1;
-        // every slot finishes within (items per slot) * chunk * max_depth segments; anything longer is a bug
-        const uint64_t iter_cap =
-            iters + (((uint64_t)(p.n_items + P - 1) / P) * chunk * (uint64_t)prm->max_depth + K - 1) / K + 4 * kBatch;
-        for (;;) {
-          if (iters > iter_cap) return set_err(c, RT_ERR_HIP, "wavefront did not drain (internal error)");
-          const uint32_t grid = (p.n + kBlock - 1) / kBlock;
-          for (int b = 0; b < kBatch; b++) {
-            if (c->timing) {
-              hipEvent_t e0 = take_event(c, ev0 + ev), e1 = take_event(c, ev0 + ev + 1);
-              if (!e0 || !e1) return set_err(c, RT_ERR_HIP, "hipEventCreate failed");
-              RT_HIP(c, hipEventRecord(e0, st));
-              launch_step<R>(p, fam, ll, nl, lli, cs.stack_need, grid, st);
-              RT_HIP(c, hipEventRecord(e1, st));
-              ev += 2;
-            } else {
-              launch_step<R>(p, fam, ll, nl, lli, cs.stack_need, grid, st);
-            }
-            launches++;
-            iters++;
-          }
-          RT_HIP(c, hipGetLastError());
-          // live-slot count; compact into a queue once half the pool has finished
-          hipLaunchKernelGGL(k_count, dim3(grid), dim3(kBlock), 0, st, (const void*)p.D, (int)f64, p.queue, p.n, blk);
-          hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, st, blk, grid, d_total);
-          launches += 2;
-          RT_HIP(c, hipMemcpyAsync(c->total_host, d_total, 4, hipMemcpyDeviceToHost, st));
-          RT_HIP(c, hipStreamSynchronize(st));
-          uint32_t alive = *c->total_host;
-          if (alive == 0) break;
-          if (p.queue || alive * 2 <= p.P) {
-            uint32_t* nq = qbuf[qsel];
-            qsel ^= 1;
-            hipLaunchKernelGGL(k_compact, dim3(grid), dim3(kBlock), 0, st, (const void*)p.D, (int)f64, p.queue, p.n,
-                               (const uint32_t*)blk, nq);
-            launches++;
-            p.queue = nq;
-            p.n = alive;
-          }
-        }
-      }
-      hipLaunchKernelGGL(k_resolve<R>, dim3((npix + kBlock - 1) / kBlock), dim3(kBlock), 0, st,
-                         (const R*)c->partial.ptr, npix, pc, spp, (R*)dout, (int)(c0 == 0),
-                         (int)(c0 + pc >= nchunks));
-      launches++;
-      RT_HIP(c, hipGetLastError());
-    }
-    // device output: nothing waits here -- the segment counters (cumulative on the device), the
-    // timing events and the fault word are settled by rt_stats, rt_reset_counters or a host-output call
-    c->ev_used = ev0 + ev;
-    c->pending = true;
-    c->pend_stream = st;
-    c->last.samples += (uint64_t)npix * spp;
-    c->last.iterations += iters;
-    c->last.launches += launches;
-  }
-  if (!out_dev) {
-    RT_HIP(c, hipMemcpyAsync(out, dout, out_elems * sizeof(R), hipMemcpyDeviceToHost, st));
-    RT_HIP(c, hipStreamSynchronize(st));
-    if ((s = settle(c)) != RT_OK) return s;
-  }
-  c->last.last_render_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  return RT_OK;
+void launch_init(const LaunchParams<R>& lp, uint32_t blocks, hipStream_t st) {
+  const Params<R> p{lp};
+  if (p.cam_mode != RT_CAM_PERSPECTIVE || p.sc.has_procedural)
+    hipLaunchKernelGGL((k_init<R, true>), dim3(blocks), dim3(kBlock), 0, st, p);
+  else
+    hipLaunchKernelGGL((k_init<R, false>), dim3(blocks), dim3(kBlock), 0, st, p);
+}
+void launch_count(const void* D, int f64, const uint32_t* queue, uint32_t n, uint32_t* blk, uint32_t* total,
+                  hipStream_t st) {
+  const uint32_t nb = (n + kBlock - 1) / kBlock;
+  hipLaunchKernelGGL(k_count, dim3(nb), dim3(kBlock), 0, st, D, f64, queue, n, blk);
+  hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, st, blk, nb, total);
+}
+void launch_compact(const void* D, int f64, const uint32_t* queue, uint32_t n, const uint32_t* blk_off, uint32_t* out,
+                    hipStream_t st) {
+  hipLaunchKernelGGL(k_compact, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, D, f64, queue, n, blk_off, out);
+}
+template <class R>
+void launch_resolve(const R* partial, uint32_t npix, uint32_t nchunks, uint32_t spp, R* out, bool first, bool last,
+                    hipStream_t st) {
+  hipLaunchKernelGGL(k_resolve<R>, dim3((npix + kBlock - 1) / kBlock), dim3(kBlock), 0, st, partial, npix, nchunks, spp,
+                     out, (int)first, (int)last);
+}
+template <class R>
+void launch_zero(R* out, uint64_t n, hipStream_t st) {
+  hipLaunchKernelGGL(k_zero<R>, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, out, n);
+}
+void launch_pixmap(const uint4* tiles, uint32_t ntiles, uint32_t npix, uint32_t* pixmap, hipStream_t st) {
+  hipLaunchKernelGGL(k_pixmap, dim3((npix + kBlock - 1) / kBlock), dim3(kBlock), 0, st, tiles, ntiles, npix, pixmap);
 }
 
-}  // namespace
+#define RT_INSTANTIATE(R)                                                                                        \
+  template void launch_zero<R>(R*, uint64_t, hipStream_t);                                                       \
+  template void launch_step<R>(const LaunchParams<R>&, KernelFamily, bool, bool, bool, int, uint32_t, hipStream_t); \
+  template void launch_init<R>(const LaunchParams<R>&, uint32_t, hipStream_t);                                   \
+  template void launch_resolve<R>(const R*, uint32_t, uint32_t, uint32_t, R*, bool, bool, hipStream_t);
+RT_INSTANTIATE(double)
+RT_INSTANTIATE(float)
+#undef RT_INSTANTIATE
 
-// ====================================================================== C ABI
-
-extern "C" {
-
-int32_t rt_abi_version(void) { return RT_ABI_VERSION; }
-
-#define RT_STR2(x) #x
-#define RT_STR(x) RT_STR2(x)
-const char* rt_build_info(void) {
-  return "dev_only=" RT_STR(RT_DEV_ONLY) " wide_top_n=" RT_STR(RT_WIDE_TOP_N) " wide_lds_stack=" RT_STR(RT_WIDE_LDS_STACK) " wide_waves_global=" RT_STR(RT_WIDE_WAVES_GLOBAL)
-#ifdef RT_SECTION_CLOCKS
-      " sections=1"
-#endif
-#ifdef RT_DEBUG_TRACE
-      " trace=1"
-#endif
-#ifdef RT_PRECISE_F32
-      " precise_f32=1"
-#endif
-      ;
-}
-#undef RT_STR
-#undef RT_STR2
-
-namespace {
 // g_sincos_tab (rt_device.h sincos2pi, fp64): (sin, cos)(2 pi j / 1024) in long double, rounded once,
 // copied to the device of the calling thread (every context's device; module globals are per device)
-hipError_t sincos_table_init() {
+hipError_t upload_sincos_table() {
   static double2 tab[kSinCosTab];
   static std::once_flag once;
   std::call_once(once, [] {
@@ -2408,178 +1683,11 @@ hipError_t sincos_table_init() {
   });
   return hipMemcpyToSymbol(HIP_SYMBOL(g_sincos_tab), tab, sizeof(tab));
 }
-}  // namespace
 
-rt_status rt_context_create(int32_t device, rt_context** out) {
-  if (!out) return set_err(nullptr, RT_ERR_INVALID_ARGUMENT, "out is null");
-  *out = nullptr;
-  int n = 0;
-  hipError_t e = hipGetDeviceCount(&n);
-  if (e != hipSuccess || n == 0) {
-    (void)hipGetLastError();
-    return set_err(nullptr, RT_ERR_NO_DEVICE, std::string("no HIP device: ") + hipGetErrorString(e));
-  }
-  if (device < 0 || device >= n) return set_err(nullptr, RT_ERR_INVALID_ARGUMENT, "device index out of range");
-  if ((e = hipSetDevice(device)) != hipSuccess) return set_err(nullptr, RT_ERR_HIP, hipGetErrorString(e));
-  if ((e = sincos_table_init()) != hipSuccess)
-    return set_err(nullptr, RT_ERR_HIP, std::string("sin/cos table: ") + hipGetErrorString(e));
-  auto* c = new rt_context;
-  c->device = device;
-  if ((e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)) != hipSuccess) {
-    delete c;
-    return set_err(nullptr, RT_ERR_HIP, hipGetErrorString(e));
-  }
-  if ((e = hipHostMalloc((void**)&c->total_host, 64 + 8 * kSegShards, hipHostMallocDefault)) != hipSuccess) {
-    (void)hipStreamDestroy(c->stream);
-    delete c;
-    return set_err(nullptr, RT_ERR_HIP, hipGetErrorString(e));
-  }
-  if (ensure(c, c->counters, sizeof(unsigned long long) * kSegShards) != RT_OK || ensure(c, c->fault, 4) != RT_OK ||
-      hipMemset(c->counters.ptr, 0, sizeof(unsigned long long) * kSegShards) != hipSuccess ||
-      hipMemset(c->fault.ptr, 0, 4) != hipSuccess) {
-    std::string m = c->err;
-    rt_context_destroy(c);
-    return set_err(nullptr, RT_ERR_OUT_OF_MEMORY, m);
-  }
-  *out = c;
-  return RT_OK;
-}
+}  // namespace rtd
 
-void rt_context_destroy(rt_context* c) {
-  if (!c) return;
-  (void)hipSetDevice(c->device);
-  // an outstanding device-output render still reads the buffers freed below (its fault word is
-  // dropped with the context: nobody is left to report it to)
-  if (c->pending) (void)hipStreamSynchronize(c->pend_stream);
-  if (c->stream) (void)hipStreamSynchronize(c->stream);
-  for (DevBuf* b : {&c->scene32, &c->scene64, &c->state, &c->partial, &c->pixmap, &c->queue0, &c->queue1, &c->blk, &c->wide_spill,
-                    &c->out_tmp, &c->counters, &c->camx, &c->heads, &c->tiles, &c->fault})
-    if (b->ptr) (void)hipFree(b->ptr);
-  for (hipEvent_t e : c->events) (void)hipEventDestroy(e);
-  if (c->total_host) (void)hipHostFree(c->total_host);
-  if (c->stream) (void)hipStreamDestroy(c->stream);
-  delete c;
-}
-
-const char* rt_last_error(const rt_context* c) {
-  if (c) return c->err.c_str();
-  std::lock_guard<std::mutex> lk(g_err_mu);
-  return g_create_err.c_str();
-}
-
-rt_status rt_scene_upload(rt_context* c, const rt_scene_desc* desc) {
-  if (!c || !desc) return set_err(c, RT_ERR_INVALID_ARGUMENT, "null context or descriptor");
-  RT_HIP(c, hipSetDevice(c->device));
-  CompiledScene cs;
-  std::string err;
-  rt_status s = compile_scene(desc, &cs, &err);
-  if (s != RT_OK) return set_err(c, s, err);
-  // renders still pending on any stream read the current scene buffers
-  if (c->pending) RT_HIP(c, hipStreamSynchronize(c->pend_stream));
-  if ((s = ensure(c, c->scene32, cs.blob32.size())) != RT_OK) return s;
-  if ((s = ensure(c, c->scene64, cs.blob64.size())) != RT_OK) return s;
-  c->scene = std::move(cs);  // copied to the device by the next render, on its stream (render<R>)
-  c->scene_dirty32 = c->scene_dirty64 = true;
-  c->has_scene = true;
-  return RT_OK;
-}
-
-rt_status rt_scene_check(const rt_scene_desc* desc, rt_scene_info* info, char* err, int32_t errlen) {
-  CompiledScene cs;
-  std::string m;
-  rt_status s = desc ? compile_scene(desc, &cs, &m) : RT_ERR_INVALID_ARGUMENT;
-  if (!desc) m = "null descriptor";
-  if (s == RT_OK) {  // the kernels a perspective render on the default (persistent) schedule would take
-    const KernelFamily fam = kernel_family(cs.hdr, RT_CAM_PERSPECTIVE, true, false);
-    if (!family_built(fam)) {
-      s = RT_ERR_UNSUPPORTED;
-      m = std::string("this build (RT_DEV_ONLY) has no ") + family_name(fam) + " kernels";
-    }
-  }
-  if (err && errlen > 0) std::snprintf(err, (size_t)errlen, "%s", m.c_str());
-  if (s == RT_OK && info) {
-    const SceneHeader& h = cs.hdr;
-    info->quads = cs.desc_quads;
-    info->flat_quads = cs.flat_quads;
-    info->flat_boxes = cs.flat_boxes;
-    info->wide_nodes = cs.hdr.has_wide ? (int32_t)cs.hdr.n_wnodes : 0;
-    info->wide_stack = cs.hdr.has_wide ? (int32_t)cs.hdr.wide_stack : 0;
-    info->wide_kinds = cs.hdr.has_wide ? (int32_t)cs.hdr.wide_kinds : 0;
-    info->wide_prim_words = cs.hdr.has_wide ? (int32_t)cs.hdr.n_wprim_words : 0;
-    info->wide_big = cs.hdr.has_wide ? (int32_t)cs.hdr.wide_big : 0;
-    info->spheres = (int32_t)h.n_spheres;
-    info->triangles = (int32_t)h.n_tris;
-    info->instances = h.num_instances;
-    info->volumes = (int32_t)h.n_volumes;
-    info->bvh_nodes = (int32_t)h.n_nodes;
-    info->linear_ops = (int32_t)h.n_linear;
-    info->stack_need = cs.stack_need;
-    info->bytes_f32 = cs.blob32.size();
-    info->bytes_f64 = cs.blob64.size();
-  }
-  return s;
-}
-
-rt_status rt_render_tiles(rt_context* c, const rt_camera_desc* cam, const rt_render_params* prm, const rt_tile* tiles,
-                          int32_t ntiles, void* out_rgb, int32_t out_is_device, void* stream) {
-  if (!c) return set_err(nullptr, RT_ERR_INVALID_ARGUMENT, "null context");
-  if (!cam || !prm || (!tiles && ntiles > 0) || ntiles < 0 || (!out_rgb && ntiles > 0))
-    return set_err(c, RT_ERR_INVALID_ARGUMENT, "null argument");
-  if (!c->has_scene) return set_err(c, RT_ERR_NO_SCENE, "rt_scene_upload has not succeeded on this context");
-  if (cam->mode < RT_CAM_PERSPECTIVE || cam->mode > RT_CAM_LENS)
-    return set_err(c, RT_ERR_INVALID_ARGUMENT, "unknown camera mode");
-  if (cam->image_width <= 0 || cam->image_height <= 0) return set_err(c, RT_ERR_INVALID_ARGUMENT, "empty image");
-  if (cam->image_width > 65535 || cam->image_height > 65535)  // pixel positions are packed x | y << 16
-    return set_err(c, RT_ERR_INVALID_ARGUMENT, "image wider or taller than 65535 pixels");
-  if (prm->spp <= 0) return set_err(c, RT_ERR_INVALID_ARGUMENT, "spp must be positive");
-  if (prm->precision != RT_PREC_F32 && prm->precision != RT_PREC_F64)
-    return set_err(c, RT_ERR_INVALID_ARGUMENT, "unknown precision");
-  for (int t = 0; t < ntiles; t++) {
-    const rt_tile& tl = tiles[t];
-    if (tl.x0 < 0 || tl.y0 < 0 || tl.width < 0 || tl.height < 0 || tl.x0 + tl.width > cam->image_width ||
-        tl.y0 + tl.height > cam->image_height)
-      return set_err(c, RT_ERR_INVALID_ARGUMENT, "tile " + std::to_string(t) + " outside the image");
-  }
-  RT_HIP(c, hipSetDevice(c->device));
-  // Device output: NULL is the HIP null stream (torch's default stream), so work the caller queues
-  // after this call on that stream -- a clone, a gather -- is ordered after the render. Host output
-  // (the call returns the finished image): NULL is the context's own non-blocking stream, so contexts
-  // driven from different host threads do not serialise on the null stream.
-  hipStream_t st = (stream == nullptr && !out_is_device) ? c->stream : (hipStream_t)stream;
-  try {
-    if (prm->precision == RT_PREC_F64) return render<double>(c, cam, prm, tiles, ntiles, out_rgb, out_is_device, st);
-    return render<float>(c, cam, prm, tiles, ntiles, out_rgb, out_is_device, st);
-  } catch (const std::bad_alloc&) {
-    return set_err(c, RT_ERR_OUT_OF_MEMORY, "out of host memory");
-  } catch (const std::exception& e) {
-    return set_err(c, RT_ERR_INVALID_ARGUMENT, e.what());
-  }
-}
-
-rt_status rt_stats(rt_context* c, rt_counters* out) {
-  if (!c || !out) return set_err(c, RT_ERR_INVALID_ARGUMENT, "null argument");
-  RT_HIP(c, hipSetDevice(c->device));
-  const rt_status s = settle(c);
-  *out = c->last;
-  return s;
-}
-
-rt_status rt_reset_counters(rt_context* c) {
-  if (!c) return set_err(nullptr, RT_ERR_INVALID_ARGUMENT, "null context");
-  RT_HIP(c, hipSetDevice(c->device));
-  const rt_status s = settle(c);  // nothing of this context is outstanding after it
-  RT_HIP(c, hipMemsetAsync(c->counters.ptr, 0, sizeof(unsigned long long) * kSegShards, c->stream));
-  if (c->fault.ptr) RT_HIP(c, hipMemsetAsync(c->fault.ptr, 0, 4, c->stream));
-  RT_HIP(c, hipStreamSynchronize(c->stream));
-  c->last = rt_counters{};
-  return s;
-}
-
-rt_status rt_set_timing(rt_context* c, int32_t enable) {
-  if (!c) return set_err(nullptr, RT_ERR_INVALID_ARGUMENT, "null context");
-  c->timing = enable ? 1 : 0;
-  return RT_OK;
-}
+// ====================================================================== development entry points
+extern "C" {
 
 #ifdef RT_ITEM_CLOCKS
 // development build only (scripts/dev_item_clocks.py): where the persistent kernels write item durations
@@ -2606,9 +1714,5 @@ void rt_dev_wide_stats(unsigned long long out[10]) {
   (void)hipMemcpyToSymbol(HIP_SYMBOL(rtd::g_wide_stats), z, sizeof(z));
 }
 #endif
-
-uint32_t rt_rng_u32(uint64_t seed, uint32_t pixel, uint32_t sample, uint32_t dim) {
-  return draw_u32(key_path(key_pixel(seed, pixel), key_sample(seed, sample)), dim);
-}
 
 }  // extern "C"

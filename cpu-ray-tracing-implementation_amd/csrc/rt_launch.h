@@ -1,0 +1,119 @@
+// rt_launch.h -- what the host code (rt_render.hip) needs to call the kernels (rt_kernels.hip): the launch
+// parameters, the constants both sides size things by, and one launch function per kernel. Internal to
+// librt_hip.so: nothing here is exported.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "rt_plan.h"
+#include "rt_types.h"
+
+namespace rtd __attribute__((visibility("hidden"))) {
+
+constexpr int kBlock = 256;
+constexpr int kSegShards = 256;  // segment counter shards
+// persistent schedule: items are handed out in batches; batch j of head h is batch j * kHeads + h of the
+// item space, so the heads interleave over the frame and a head that runs dry steals from the others
+constexpr uint32_t kHeads = 8;
+constexpr uint32_t kHeadStride = 64;  // 256 B apart: one L2 line per head
+
+template <class R>
+struct alignas(4 * sizeof(R)) R4 {
+  R x, y, z, w;
+};
+
+// Path state in HBM (wavefront schedule), one entry per slot, structure of arrays of 16-byte (fp32)
+// or 32-byte (fp64) records so every access is a coalesced dwordx4:
+//   O  origin, ray time            D  direction, bounce (-1: slot retired)
+//   T  throughput                  L  radiance of the running sample
+//   A  running sum of the item     S  key_pixel, key of the running sample, item, sample
+//   X  the surface the ray leaves (entry, instance): self-intersection exclusion;
+//      the pixel (x | y << 16) and the end of the sample range of the slot's item
+template <class R>
+struct LaunchParams {
+  DevScene<R> sc;
+  R4<R>* O;
+  R4<R>* D;
+  R4<R>* T;
+  R4<R>* L;
+  R4<R>* A;
+  uint4* S;
+  uint4* X;
+  R* partial;              // per item: 3 sums
+  const uint32_t* pixmap;  // local pixel -> its image position x | y << 16
+  const uint32_t* queue;   // live slots, or null = slots [0, n)
+  uint32_t n;
+  uint32_t P, npix, n_items, chunk, spp, first_sample, W;
+  // two item sizes: chunks [0, k_bulk) hold `chunk` samples, the later ones (the frame's last
+  // items in dequeue order) `tail_chunk` <= chunk samples each (rt_plan.h ItemPlan)
+  uint32_t k_bulk, tail_chunk;
+  // the render's chunks come in passes (the partial sums of one pass fit a memory budget): this
+  // launch's items are chunks [chunk0, chunk0 + n_items / npix) of every pixel
+  uint32_t chunk0;
+  uint64_t npix_m;  // item / npix = (item * npix_m) >> npix_k for every item < 2^31 (div_magic)
+  uint32_t npix_k;
+  int32_t max_depth;
+  uint64_t seed;
+  // camera rays are built in fp64 for both paths (fp32 rounds once), from CamDev in device
+  // memory (scalar loads at the point of use)
+  int32_t cam_mode;
+  const CamDev* camx;
+  unsigned long long* seg_shards;
+  int32_t K;  // segments per launch
+  // kPersist: the persistent schedule (k_persist), one launch whose grid is what the chip holds resident and
+  // whose lanes pull items from the per-XCD heads. 0: the wavefront schedule (k_init, k_step), slot s owns
+  // items s, s + P, ...
+  int32_t persist;
+  uint32_t* heads;  // kHeads dequeue counters, kHeadStride words apart (persistent schedule)
+  uint64_t seg_cap;  // a lane never needs more segments than this (its items * chunk * max_depth)
+  uint32_t* fault;   // set when a lane hits seg_cap (internal error, reported by the host)
+};
+constexpr int32_t kPersist = 2;
+
+// RT_DEV_ONLY (development builds for register/spill iteration, scripts/kernel_usage.py): instantiate one
+// kernel family only -- 1 the flat program, 2 the wide BVH, 3 the quad + volume linear program. 0:
+// everything. A render (and rt_scene_check) that needs a family such a build omits fails with
+// RT_ERR_UNSUPPORTED instead of launching nothing.
+#ifndef RT_DEV_ONLY
+#define RT_DEV_ONLY 0
+#endif
+constexpr bool family_built(KernelFamily f) {
+  return RT_DEV_ONLY == 0 || (RT_DEV_ONLY == 1 && f == KF_FLAT) || (RT_DEV_ONLY == 2 && f == KF_WIDE) ||
+         (RT_DEV_ONLY == 3 && f == KF_LIN_VOL);
+}
+
+// Waves per SIMD of the fp32 wide-BVH kernel over a tree in HBM (WideTrav::kWaves; here because rt_build_info
+// reports it): 32-bit stack in LDS (C4 stand-in: 4 waves 519 ms, 5: 462; with the speculative traversal 5: 424,
+// 6: 412.5 -- 7 blocks of 24 KB stacks do not fit the 160 KB LDS)
+#ifndef RT_WIDE_WAVES_GLOBAL
+#define RT_WIDE_WAVES_GLOBAL 8  // round 5, with 12 LDS stack entries and 55 top nodes in LDS (wide_lds_stack)
+#endif
+
+// One launch of the render's path kernel (k_persist* or k_step* of the family): `grid` blocks at most (the
+// persistent schedule cuts it to the resident blocks). ll / nl / lli: the scene-class predicates of
+// rt_plan.h; stack: the binary BVH's stack need. Defined for float and double.
+template <class R>
+void launch_step(const LaunchParams<R>& p, KernelFamily fam, bool ll, bool nl, bool lli, int stack, uint32_t grid,
+                 hipStream_t st);
+uint64_t last_grid_lanes();  // lanes of the last persistent launch_step on this host thread
+
+// wavefront schedule: the first camera ray of every slot; live-slot count and compaction
+template <class R>
+void launch_init(const LaunchParams<R>& p, uint32_t blocks, hipStream_t st);
+void launch_count(const void* D, int f64, const uint32_t* queue, uint32_t n, uint32_t* blk, uint32_t* total,
+                  hipStream_t st);  // k_count + k_scan: blk = exclusive block offsets, *total = live slots
+void launch_compact(const void* D, int f64, const uint32_t* queue, uint32_t n, const uint32_t* blk_off, uint32_t* out,
+                    hipStream_t st);
+
+template <class R>
+void launch_resolve(const R* partial, uint32_t npix, uint32_t nchunks, uint32_t spp, R* out, bool first, bool last,
+                    hipStream_t st);
+template <class R>
+void launch_zero(R* out, uint64_t n, hipStream_t st);
+void launch_pixmap(const uint4* tiles, uint32_t ntiles, uint32_t npix, uint32_t* pixmap, hipStream_t st);
+
+// the fp64 sin/cos table (rt_device.h g_sincos_tab) copied to the calling thread's device
+hipError_t upload_sincos_table();
+
+}  // namespace rtd

@@ -1,0 +1,144 @@
+// rt_plan.h -- the host's decisions about a render, as pure functions of the compiled scene's header and the
+// call's sizes: which kernel family it takes, and how its samples are cut into work items and passes. No
+// HIP and no environment access, so the decisions are testable without a GPU (tests/test_plan.py).
+#pragma once
+
+#include <stdint.h>
+
+#include <algorithm>
+
+#include "../../include/rt_hip.h"
+#include "rt_scene.h"
+
+namespace rtd {
+
+// Division by a launch constant d >= 1 as a multiply (Granlund-Montgomery): with
+// k = 32 + ceil(log2 d) and m = floor(2^k / d) + 1, (n * m) >> k == n / d for every n < 2^31
+// (m d - 2^k <= d, so the error n (m d - 2^k) / 2^k stays below 1/d; n m < 2^64).
+inline void div_magic(uint32_t d, uint64_t& m, uint32_t& k) {
+  uint32_t l = 0;
+  while ((1ull << l) < d) l++;
+  k = 32 + l;
+  m = (uint64_t)((((unsigned __int128)1) << k) / d) + 1;
+}
+
+// The kernel family a render takes, decided from the compiled scene, the camera model, the schedule and the
+// traversal order (launch_step launches it).
+enum KernelFamily { KF_FLAT, KF_LIN_QUAD, KF_LIN_VOL, KF_LIN_SPH, KF_LIN_ALL, KF_WIDE, KF_STACK };
+inline KernelFamily kernel_family(const SceneHeader& h, int32_t cam_mode, bool persist, bool ordered) {
+  const bool persp = cam_mode == RT_CAM_PERSPECTIVE, procedural = h.n_texdata > 0 || h.has_cell_noise;
+  const bool sph = h.n_spheres > 0, tri = h.n_tris > 0, vol = h.has_volumes != 0;
+  // the flat program (world-space quads and boxes, fp32 and fp64); the extended kernels keep the linear one
+  if (!ordered && h.has_flat && persp && !procedural) return KF_FLAT;
+  if (h.n_linear > 0) {
+    if (!sph && !tri) return vol ? KF_LIN_VOL : KF_LIN_QUAD;
+    return (sph && !tri && !vol) ? KF_LIN_SPH : KF_LIN_ALL;
+  }
+  // the wide BVH (persistent schedule, base kernels; fp64 rays since round 3)
+  if (!ordered && h.has_wide && persist && persp && !procedural) return KF_WIDE;
+  return KF_STACK;
+}
+inline const char* family_name(KernelFamily f) {
+  static const char* n[] = {"flat program", "linear program (quads)", "linear program (quads + volumes)",
+                            "linear program (spheres)", "linear program (all kinds)", "wide BVH", "binary BVH"};
+  return n[f];
+}
+
+// a lambertian + diffuse_light scene with solid textures (a background too) and an axis-aligned quad light (the
+// Cornell configs): the flat kernel's LL form (shade LL)
+inline bool lamb_light_scene(const SceneHeader& h) {
+  const uint32_t ok_m = (1u << M_LAMBERTIAN) | (1u << M_DIFFUSE_LIGHT);
+  return (h.mat_kinds & ~ok_m) == 0 && (h.tex_kinds & ~(1u << T_SOLID)) == 0 && h.light_kind == L_QUAD &&
+         h.light_aligned != 0;
+}
+// no light, lambertian / metal / dielectric materials with solid or checker textures (RTOW): shade NL
+inline bool no_light_scene(const SceneHeader& h) {
+  const uint32_t ok_m = (1u << M_LAMBERTIAN) | (1u << M_METAL) | (1u << M_DIELECTRIC);
+  return (h.mat_kinds & ~ok_m) == 0 && (h.tex_kinds & ~((1u << T_SOLID) | (1u << T_CHECKER))) == 0 &&
+         h.light_kind == L_NONE;
+}
+// lambertian, isotropic and diffuse_light materials with solid textures and an axis-aligned quad light (C5)
+inline bool lamb_iso_light_scene(const SceneHeader& h) {
+  const uint32_t ok_m = (1u << M_LAMBERTIAN) | (1u << M_DIFFUSE_LIGHT) | (1u << M_ISOTROPIC);
+  return (h.mat_kinds & ~ok_m) == 0 && (h.tex_kinds & ~(1u << T_SOLID)) == 0 && h.light_kind == L_QUAD &&
+         h.light_aligned != 0;
+}
+
+// ------------------------------------------------------------------ the item layout
+// Work item = (pixel, chunk of consecutive samples). The layout decides the image's summation order (per
+// pixel: samples within an item, then items in chunk order), the item count (below 2^31 per launch) and the
+// partial-sum memory, so it depends on spp and the full image alone: the same for any tiling or rank count.
+//
+// The automatic sizes (rt_render_params.samples_per_item = 0); the caller may override them for A/B runs
+// (RT_ITEM_*, RT_ITEMS_TARGET, RT_PARTIAL_BUDGET in the environment; scripts/dev_tail.py). `flat`: the flat
+// program's, whose items are cheaper per sample, so its default items are longer (fewer item ends, dequeues
+// and partial-sum stores; C2: 23.9 -> 23.5 ms/frame).
+// Bulk items: 8 samples (32 for the flat program); at most kMaxItemsPerPixel items per pixel in all (both
+// sizes doubled until they fit), so a high-spp frame (C5: 3840x2160 at 4096 spp) keeps its item count under
+// 2^31 and its partial sums bounded.
+constexpr uint32_t kMaxItemsPerPixel = 256;
+constexpr uint32_t kMinAutoChunk = 2;
+struct PlanKnobs {
+  uint32_t chunk = 8, chunk_flat = 32;        // bulk item size
+  uint32_t tail_chunk = 4, tail_chunk_flat = 8;  // size of the frame's last items
+  double tail_frac = 0.5, tail_frac_flat = 0.125;  // share of every pixel's samples in tail items
+  // items a frame should have at least. C1 (400x400, 64 spp), ms/frame by target (item size): fp64 none (16)
+  // 0.918, 1 M (8) 0.792, 2.5 M (4) 0.735, 5 M (2) 0.710; fp32 none (32 + tail items of 8) 0.661, 1 M 0.589,
+  // 2.5 M 0.525, 5 M 0.536. The BASELINE configs from C2 up have 40 M items or more and keep their sizes.
+  uint64_t items_target = 4000000;
+  // item partial sums of one pass at most (a call needing more renders its chunks in passes)
+  uint64_t partial_budget = 2ull << 30;
+};
+
+// Chunks [0, k_bulk) of a pixel hold `chunk` samples, chunks [k_bulk, nchunks) `tail_chunk` <= chunk (the
+// last one what is left of spp). The chunks come in `passes` launches of at most `cpp` chunks each.
+struct ItemPlan {
+  uint32_t chunk, tail_chunk, k_bulk, nchunks;
+  uint32_t cpp;            // chunks per pass
+  uint32_t passes;
+  uint64_t partial_bytes;  // partial sums of the largest pass: 3 elements per item
+};
+
+// spp >= 1; samples_per_item <= 0: the automatic layout; full_pixels: the whole image's; npix >= 1: this
+// call's (its tiles'), below 2^31; elem: bytes of a partial sum's element (4 or 8).
+inline ItemPlan plan_items(uint32_t spp, int32_t samples_per_item, bool flat, uint64_t full_pixels, uint32_t npix,
+                           uint32_t elem, const PlanKnobs& kn) {
+  const bool automatic = samples_per_item <= 0;
+  uint32_t chunk0 = std::min(spp, automatic ? std::max(1u, flat ? kn.chunk_flat : kn.chunk) : (uint32_t)samples_per_item);
+  // a small frame (C1: 160,000 px x 64 spp is ~2 items of 16 per resident lane) takes smaller items, so
+  // the lanes that finish early find work while the last items run: the automatic size is halved until
+  // the whole frame has items_target items
+  if (automatic)
+    while (chunk0 > kMinAutoChunk && full_pixels * ((spp + chunk0 - 1) / chunk0) < kn.items_target) chunk0 /= 2;
+  ItemPlan pl{};
+  pl.chunk = pl.tail_chunk = chunk0;
+  pl.k_bulk = pl.nchunks = (spp + chunk0 - 1) / chunk0;
+  // The frame's last items are short (automatic layout only): a lane that takes a long item just
+  // before the queue runs dry keeps its wave resident while the others idle, and a small frame
+  // (one rank of eight) has few items per lane. The last tail_samples of every pixel come in
+  // items of tail_chunk samples. (fp64 too since round 3: round 2 kept uniform items of 16 for it)
+  if (automatic) {
+    const double frac = std::min(1.0, std::max(0.0, flat ? kn.tail_frac_flat : kn.tail_frac));
+    const uint32_t ts = std::min<uint32_t>(spp, (uint32_t)((double)spp * frac + 0.5));
+    pl.tail_chunk = std::min(pl.chunk, std::max(1u, flat ? kn.tail_chunk_flat : kn.tail_chunk));
+    for (;;) {
+      pl.k_bulk = (spp - ts) / pl.chunk;  // bulk items cover [0, k_bulk * chunk)
+      pl.nchunks = pl.k_bulk + (spp - pl.k_bulk * pl.chunk + pl.tail_chunk - 1) / pl.tail_chunk;
+      if (pl.nchunks <= kMaxItemsPerPixel || pl.chunk >= spp) break;
+      pl.chunk = std::min(spp, 2 * pl.chunk);
+      pl.tail_chunk = std::min(pl.chunk, 2 * pl.tail_chunk);
+    }
+  }
+  // Passes: the item partial sums of a call are 3 elements per (pixel, chunk) -- C5 fp64 (3840 x 2160 at
+  // 4096 spp, 192 chunks) would need 38 GB. The chunks come in passes of `cpp` chunks whose partial sums fit
+  // the budget (and whose items fit 31 bits); every pass is one launch, and its resolve adds its chunks to
+  // the running per-pixel sums in chunk order (k_resolve), so the image is the same for any split.
+  const uint64_t per_chunk = 3ull * elem * npix;
+  pl.cpp = (uint32_t)std::max<uint64_t>(
+      1, std::min<uint64_t>({(uint64_t)pl.nchunks, kn.partial_budget / per_chunk, ((1ull << 31) - 1) / npix}));
+  pl.passes = (pl.nchunks + pl.cpp - 1) / pl.cpp;
+  pl.partial_bytes = per_chunk * pl.cpp;
+  return pl;
+}
+
+}  // namespace rtd

@@ -1,0 +1,698 @@
+// rt_render.hip -- the host side of librt_hip.so: contexts and their device buffers, render<R>() and its two
+// schedules, and the C ABI of include/rt_hip.h. It contains no kernel: what a render launches goes through
+// rt_launch.h (rt_kernels.hip), and its item layout and kernel family come from rt_plan.h.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <mutex>
+#include <new>
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+#include "../../include/rt_hip.h"
+#include "rt_launch.h"
+#include "rt_plan.h"
+#include "scene_compile.h"
+
+using namespace rtd;
+
+struct DevBuf {
+  void* ptr = nullptr;
+  size_t bytes = 0;
+};
+
+struct rt_context {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  std::string err;
+  CompiledScene scene;
+  bool has_scene = false;
+  DevBuf scene32, scene64;
+  DevBuf state, partial, pixmap, queue0, queue1, blk, out_tmp, counters, camx, heads, tiles;
+  DevBuf wide_spill;  // the wide traversal's stack entries past wide_lds_stack (deep trees in HBM)
+  CamDev cam_host;  // source of camx (kept alive for the async copy)
+  uint32_t* total_host = nullptr;  // pinned: [0] live slots, [1] fault word, [16..] segment counter shards
+  uint64_t samples = 0;
+  rt_counters last{};  // host-known totals since rt_reset_counters; segments and step_ms settle in settle()
+  int timing = 0;
+  std::vector<hipEvent_t> events;
+  // asynchronous renders (device output): what rt_stats / rt_reset_counters / a host-output render
+  // settle with one sync -- the stream, the timing events recorded since the last settle
+  hipStream_t pend_stream = nullptr;
+  bool pending = false;
+  size_t ev_used = 0;
+  DevBuf fault;  // sticky internal-error word of the persistent kernel (zeroed by rt_reset_counters)
+  // inputs kept on the device while they do not change between calls
+  std::vector<uint4> tiles_dev;  // the tile list k_pixmap last expanded into pixmap
+  void* pixmap_for = nullptr;    // pixmap buffer that expansion went to
+  uint32_t pixmap_npix = 0;      // pixels it expanded: a tile entry {x0, y0, width, first} does not
+                                 // hold the height, so the last tile can change with the list equal
+  CamDev cam_dev{};              // the camera view in camx
+  bool cam_valid = false;
+  // the compiled scene is copied into scene32 / scene64 by the first render after rt_scene_upload,
+  // on that render's stream: a copy made on another stream is not guaranteed visible to the kernels
+  // of the render stream (their launch need not invalidate the L2 lines of the previous scene)
+  bool scene_dirty32 = false, scene_dirty64 = false;
+};
+
+namespace {
+
+// camera.h:137-141, 246, 253, 278-279 evaluated in double exactly as the reference orders them
+CamDev make_view(const rt_camera_desc* c) {
+  CamDev v{};
+  v.mode = c->mode;
+  double du[3], dv[3], dir00[3], pos00[3];
+  for (int k = 0; k < 3; k++) {
+    du[k] = (c->right[k] * c->viewport_width) / (double)c->image_width;
+    dv[k] = (c->up[k] * -c->viewport_height) / (double)c->image_height;
+  }
+  for (int k = 0; k < 3; k++) {
+    double a = c->dir[k] * c->focal_length;
+    double b = c->right[k] * (c->viewport_width / 2.0);
+    double u = c->up[k] * (c->viewport_height / 2.0);
+    double e = (du[k] + dv[k]) * 0.5;
+    dir00[k] = ((a - b) + u) + e;
+    pos00[k] = ((c->pos[k] - b) + u) + e;
+  }
+  v.pos = {c->pos[0], c->pos[1], c->pos[2]};
+  v.du = {du[0], du[1], du[2]};
+  v.dv = {dv[0], dv[1], dv[2]};
+  v.dir00 = {dir00[0], dir00[1], dir00[2]};
+  v.pos00 = {pos00[0], pos00[1], pos00[2]};
+  v.dir = {c->dir[0], c->dir[1], c->dir[2]};
+  v.fdir = {c->focus_dist * c->dir[0], c->focus_dist * c->dir[1], c->focus_dist * c->dir[2]};
+  v.disk_u = {c->defocus_u[0], c->defocus_u[1], c->defocus_u[2]};
+  v.disk_v = {c->defocus_v[0], c->defocus_v[1], c->defocus_v[2]};
+  v.focal = c->focal_length;
+  return v;
+}
+
+std::mutex g_err_mu;
+std::string g_create_err;
+
+rt_status set_err(rt_context* c, rt_status s, const std::string& m) {
+  if (c) {
+    c->err = m;
+  } else {
+    std::lock_guard<std::mutex> lk(g_err_mu);
+    g_create_err = m;
+  }
+  return s;
+}
+
+#define RT_HIP(ctx, call)                                                                   \
+  do {                                                                                      \
+    hipError_t e_ = (call);                                                                 \
+    if (e_ != hipSuccess)                                                                   \
+      return set_err((ctx), RT_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
+  } while (0)
+
+// Grow a context buffer. The only work that can still read the old buffer is this context's
+// outstanding device-output render (host-output renders return finished, and a render on another
+// stream waits for pend_stream first): wait for that stream, not for the whole device.
+rt_status ensure(rt_context* c, DevBuf& b, size_t bytes) {
+  if (b.ptr && b.bytes >= bytes) return RT_OK;
+  if (b.ptr) {
+    if (c->pending) RT_HIP(c, hipStreamSynchronize(c->pend_stream));
+    RT_HIP(c, hipFree(b.ptr));
+    b.ptr = nullptr;
+    b.bytes = 0;
+  }
+  size_t want = std::max<size_t>(bytes, 256);
+  hipError_t e = hipMalloc(&b.ptr, want);
+  if (e != hipSuccess) {
+    b.ptr = nullptr;
+    (void)hipGetLastError();
+    return set_err(c, RT_ERR_OUT_OF_MEMORY,
+                   "hipMalloc(" + std::to_string(want) + " bytes): " + hipGetErrorString(e));
+  }
+  b.bytes = want;
+  return RT_OK;
+}
+
+hipEvent_t take_event(rt_context* c, size_t idx) {
+  while (c->events.size() <= idx) {
+    hipEvent_t e = nullptr;
+    if (hipEventCreate(&e) != hipSuccess) return nullptr;
+    c->events.push_back(e);
+  }
+  return c->events[idx];
+}
+
+// Wait for the context's outstanding renders and fold their device-side results into c->last:
+// the cumulative segment count, the kernel time of the timing events, the fault word.
+rt_status settle(rt_context* c) {
+  if (!c->pending) return RT_OK;
+  c->pending = false;
+  RT_HIP(c, hipStreamSynchronize(c->pend_stream));
+  unsigned long long* shards = (unsigned long long*)(c->total_host + 16);
+  RT_HIP(c, hipMemcpy(shards, c->counters.ptr, sizeof(unsigned long long) * kSegShards, hipMemcpyDeviceToHost));
+  uint64_t segs = 0;
+  for (int k = 0; k < kSegShards; k++) segs += shards[k];
+  c->last.segments = segs;
+  double ms = 0;
+  for (size_t k = 0; k + 1 < c->ev_used; k += 2) {
+    float a = 0;
+    RT_HIP(c, hipEventElapsedTime(&a, c->events[k], c->events[k + 1]));
+    ms += a;
+  }
+  c->ev_used = 0;
+  c->last.step_ms += ms;
+  uint32_t fault = 0;
+  if (c->fault.ptr) RT_HIP(c, hipMemcpy(&fault, c->fault.ptr, 4, hipMemcpyDeviceToHost));
+  if (fault) return set_err(c, RT_ERR_HIP, "a path did not finish (internal error)");
+  return RT_OK;
+}
+
+template <class R>
+DevScene<R> dev_scene(const SceneHeader& h, void* base) {
+  auto at = [&](uint64_t off) { return (const unsigned char*)base + off; };
+  DevScene<R> s{};
+  s.quads = (const Quad<R>*)at(h.off_quads);
+  s.spheres = (const Sphere<R>*)at(h.off_spheres);
+  s.tris = (const Tri<R>*)at(h.off_tris);
+  s.insts = (const Instance<R>*)at(h.off_instances);
+  s.vols = (const Volume<R>*)at(h.off_volumes);
+  s.nodes = (const Node<R>*)at(h.off_nodes);
+  s.refs = (const uint32_t*)at(h.off_refs);
+  s.mats = (const Material<R>*)at(h.off_mats);
+  s.texs = (const Texture<R>*)at(h.off_texs);
+  s.light = (const Light<R>*)at(h.off_light);
+  s.lin = (const LinRec<R>*)at(h.off_linear);
+  s.n_linear = h.n_linear;
+  s.has_flat = (int32_t)h.has_flat;
+  s.flatq = (const FlatQuadT<R>*)at(h.off_flat_quad);
+  s.flatb = (const FlatBoxT<R>*)at(h.off_flat_box);
+  for (int a = 0; a < 3; a++) s.n_flatq[a] = h.n_flat_quad[a];
+  s.n_flatb = h.n_flat_box;
+  s.n_mats = h.n_mats;
+  s.root = h.root;
+  s.background = h.background;
+  s.has_volumes = h.has_volumes;
+  s.n_nodes = h.n_nodes;
+  s.texdata = (const double*)at(h.off_texdata);
+  s.images = (const uint8_t*)at(h.off_images);
+  s.has_procedural = h.n_texdata > 0 || h.has_cell_noise;
+  s.has_wide = (int32_t)h.has_wide;
+  s.wnodes = (const WNode*)at(h.off_wnodes);
+  s.wprims = (const typename WWord<R>::T*)at(h.off_wprims);
+  s.n_wnodes = h.n_wnodes;
+  s.n_wprim_words = h.n_wprim_words;
+  s.wroot = h.wroot;
+  s.wide_stack = h.wide_stack;
+  s.wide_kinds = h.wide_kinds;
+  s.wide_big = h.wide_big;
+  s.wide_top = h.wide_top;
+  s.wnodesh = h.has_wnodesh ? (const WNodeH*)at(h.off_wnodesh) : nullptr;
+  s.quads64 = h.has_quads64 ? (const Quad<double>*)at(h.off_quads64) : nullptr;
+  return s;
+}
+
+constexpr int kBatch = 16;  // wavefront schedule: extend/shade rounds between live-slot counts
+constexpr uint32_t kAutoPool32 = 1u << 21;
+constexpr uint32_t kAutoPool64 = 1u << 19;
+constexpr int kAutoSegments = 16;  // segments each slot advances per k_step launch
+// persistent schedule: upper bound of the grid's lanes (launch_step cuts the grid to what the chip holds resident)
+constexpr uint32_t kAutoPersistLanes = 1u << 22;
+
+// The item layout's knobs (rt_plan.h): RT_ITEM_*, RT_ITEMS_TARGET and RT_PARTIAL_BUDGET in the environment override
+// the defaults for A/B runs (scripts/dev_tail.py, tests/test_gpu_passes.py)
+PlanKnobs env_knobs() {
+  auto num = [](const char* name, double dflt) {
+    const char* v = std::getenv(name);
+    return (v && *v) ? std::strtod(v, nullptr) : dflt;
+  };
+  PlanKnobs k;
+  k.chunk = (uint32_t)num("RT_ITEM_CHUNK", k.chunk);
+  k.chunk_flat = (uint32_t)num("RT_ITEM_CHUNK_FLAT", k.chunk_flat);
+  k.tail_chunk = (uint32_t)num("RT_ITEM_TAIL_CHUNK", k.tail_chunk);
+  k.tail_chunk_flat = (uint32_t)num("RT_ITEM_TAIL_CHUNK_FLAT", k.tail_chunk_flat);
+  k.tail_frac = num("RT_ITEM_TAIL_FRAC", k.tail_frac);
+  k.tail_frac_flat = num("RT_ITEM_TAIL_FRAC_FLAT", k.tail_frac_flat);
+  k.items_target = (uint64_t)num("RT_ITEMS_TARGET", (double)k.items_target);
+  k.partial_budget = (uint64_t)num("RT_PARTIAL_BUDGET", (double)k.partial_budget);
+  return k;
+}
+
+// What launch_step needs besides the parameters
+struct StepKind {
+  KernelFamily fam;
+  bool ll, nl, lli;
+  int stack;
+};
+
+// One launch_step, between two events when the context collects kernel times (settle() sums the pairs)
+template <class R>
+rt_status timed_step(rt_context* c, const LaunchParams<R>& p, const StepKind& k, uint32_t grid, hipStream_t st) {
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (c->timing) {
+    e0 = take_event(c, c->ev_used);
+    e1 = take_event(c, c->ev_used + 1);
+    if (!e0 || !e1) return set_err(c, RT_ERR_HIP, "hipEventCreate failed");
+    RT_HIP(c, hipEventRecord(e0, st));
+  }
+  launch_step<R>(p, k.fam, k.ll, k.nl, k.lli, k.stack, grid, st);
+  if (c->timing) {
+    RT_HIP(c, hipEventRecord(e1, st));
+    c->ev_used += 2;
+  }
+  c->last.launches++;
+  c->last.iterations++;
+  return RT_OK;
+}
+
+// The persistent schedule (the default): one launch of at most `grid` blocks renders the pass. A fault is
+// reported by the settle after the call (rt_stats, or a host-output render).
+template <class R>
+rt_status run_persistent(rt_context* c, const LaunchParams<R>& p, const StepKind& k, uint32_t grid, hipStream_t st) {
+  RT_HIP(c, hipMemsetAsync(c->heads.ptr, 0, 4ull * kHeads * kHeadStride, st));
+  rt_status s;
+  if ((s = timed_step(c, p, k, grid, st)) != RT_OK) return s;
+  RT_HIP(c, hipGetLastError());
+  c->last.grid_lanes = last_grid_lanes();
+  return RT_OK;
+}
+
+// The wavefront schedule (segments_per_launch = K > 0): P slots with their path state in HBM, one launch per K
+// segments, the live slots counted every kBatch launches and compacted into a queue once half have finished.
+template <class R>
+rt_status run_wavefront(rt_context* c, LaunchParams<R> p, const StepKind& k, uint32_t nblk_max, hipStream_t st) {
+  const uint32_t P = p.P;
+  p.queue = nullptr;
+  p.n = P;
+  launch_init<R>(p, nblk_max, st);
+  c->last.launches++;
+  uint32_t* qbuf[2] = {(uint32_t*)c->queue0.ptr, (uint32_t*)c->queue1.ptr};
+  int qsel = 0;
+  uint32_t* blk = (uint32_t*)c->blk.ptr;
+  uint32_t* d_total = blk + nblk_max + 1;
+  // every slot finishes within (items per slot) * chunk * max_depth segments; anything longer is a bug
+  const uint64_t iter_cap =
+      c->last.iterations + (((uint64_t)(p.n_items + P - 1) / P) * p.chunk * (uint64_t)p.max_depth + p.K - 1) / p.K + 4 * kBatch;
+  for (;;) {
+    if (c->last.iterations > iter_cap) return set_err(c, RT_ERR_HIP, "wavefront did not drain (internal error)");
+    const uint32_t grid = (p.n + kBlock - 1) / kBlock;
+    rt_status s;
+    for (int b = 0; b < kBatch; b++)
+      if ((s = timed_step(c, p, k, grid, st)) != RT_OK) return s;
+    RT_HIP(c, hipGetLastError());
+    // live-slot count; compact into a queue once half the pool has finished
+    launch_count(p.D, sizeof(R) == 8, p.queue, p.n, blk, d_total, st);
+    c->last.launches += 2;
+    RT_HIP(c, hipMemcpyAsync(c->total_host, d_total, 4, hipMemcpyDeviceToHost, st));
+    RT_HIP(c, hipStreamSynchronize(st));
+    const uint32_t alive = *c->total_host;
+    if (alive == 0) return RT_OK;
+    if (p.queue || alive * 2 <= P) {
+      uint32_t* nq = qbuf[qsel];
+      qsel ^= 1;
+      launch_compact(p.D, sizeof(R) == 8, p.queue, p.n, blk, nq, st);
+      c->last.launches++;
+      p.queue = nq;
+      p.n = alive;
+    }
+  }
+}
+
+template <class R>
+rt_status render(rt_context* c, const rt_camera_desc* cam, const rt_render_params* prm, const rt_tile* tiles,
+                 int32_t ntiles, void* out, int32_t out_dev, hipStream_t st) {
+  const bool f64 = sizeof(R) == 8;
+  const CompiledScene& cs = c->scene;
+  const SceneHeader& hdr = f64 ? cs.hdr64 : cs.hdr;
+  void* sbase = f64 ? c->scene64.ptr : c->scene32.ptr;
+  bool& dirty = f64 ? c->scene_dirty64 : c->scene_dirty32;
+  auto t0 = std::chrono::steady_clock::now();
+  // A device-output render still pending on another stream reads the context's shared buffers
+  // (pixmap, tiles, camx, heads, partial): wait for it before this call writes any of them.
+  if (c->pending && c->pend_stream != st) RT_HIP(c, hipStreamSynchronize(c->pend_stream));
+  if (dirty) {  // the scene uploaded since the last render of this precision, stream-ordered before its kernels
+    const std::vector<unsigned char>& blob = f64 ? cs.blob64 : cs.blob32;
+    RT_HIP(c, hipMemcpyAsync(sbase, blob.data(), blob.size(), hipMemcpyHostToDevice, st));
+    dirty = false;
+    // outstanding from here on, whatever this call does next (an empty tile list or max_depth <= 0
+    // launches nothing that reads the scene): a later render on another stream waits for st
+    c->pending = true;
+    c->pend_stream = st;
+  }
+
+  // pixel map: tiles packed in order, row-major inside each tile (expanded by k_pixmap)
+  std::vector<uint4> tl;
+  tl.reserve(ntiles);
+  uint64_t npix64 = 0;
+  for (int t = 0; t < ntiles; t++) {
+    if (tiles[t].width == 0 || tiles[t].height == 0) continue;
+    tl.push_back(make_uint4((uint32_t)tiles[t].x0, (uint32_t)tiles[t].y0, (uint32_t)tiles[t].width, (uint32_t)npix64));
+    npix64 += (uint64_t)tiles[t].width * (uint64_t)tiles[t].height;
+  }
+  if (npix64 >= (1ull << 31)) return set_err(c, RT_ERR_INVALID_ARGUMENT, "too many pixels in one call");
+  const uint32_t npix = (uint32_t)npix64;
+  if (npix == 0) return RT_OK;
+  const size_t out_elems = 3ull * npix;
+  rt_status s;
+  void* dout = out;
+  if (!out_dev) {
+    if ((s = ensure(c, c->out_tmp, out_elems * sizeof(R))) != RT_OK) return s;
+    dout = c->out_tmp.ptr;
+  }
+
+  if (prm->max_depth <= 0) {  // ray_color(r, 0) is black for every sample (camera.h:194-195)
+    launch_zero<R>((R*)dout, (uint64_t)out_elems, st);
+  } else {
+    const uint32_t spp = (uint32_t)prm->spp;
+    // the default schedule is persistent (k_persist); an explicit segments_per_launch selects the
+    // launch-per-K-segments wavefront with HBM path state and live-slot compaction
+    const bool persist = prm->segments_per_launch <= 0;
+    const StepKind kind{kernel_family(hdr, cam->mode, persist, prm->traversal == RT_TRAV_ORDERED), lamb_light_scene(hdr),
+                        no_light_scene(hdr), lamb_iso_light_scene(hdr), cs.stack_need};
+    if (!family_built(kind.fam))
+      return set_err(c, RT_ERR_UNSUPPORTED,
+                     std::string("this build (RT_DEV_ONLY) has no ") + family_name(kind.fam) + " kernels");
+    // the item layout and the passes (the full image's pixels decide the item size, not this call's tiles)
+    const ItemPlan plan = plan_items(spp, prm->samples_per_item, kind.fam == KF_FLAT,
+                                     (uint64_t)cam->image_width * (uint64_t)cam->image_height, npix, sizeof(R), env_knobs());
+    const uint32_t n_items = npix * plan.cpp;  // items of the largest pass
+    uint32_t P = prm->pool_slots > 0 ? (uint32_t)prm->pool_slots
+                 : persist       ? kAutoPersistLanes
+                                 : (f64 ? kAutoPool64 : kAutoPool32);
+    P = std::max<uint32_t>(1, std::min(P, n_items));
+    const uint32_t nblk_max = (P + kBlock - 1) / kBlock;
+
+    // path state: 5 R4 arrays (O, D, T, L, A) + uint4 keys (S) + uint4 exclusion/pixel (X), each P long
+    auto al = [](size_t x) { return (x + 255) & ~size_t(255); };
+    const size_t r4 = al(sizeof(R4<R>) * (size_t)P), sb = al(16 * (size_t)P), xb = al(16 * (size_t)P);
+    if (!persist) {
+      if ((s = ensure(c, c->state, 5 * r4 + sb + xb)) != RT_OK) return s;
+      if ((s = ensure(c, c->queue0, 4ull * P)) != RT_OK) return s;
+      if ((s = ensure(c, c->queue1, 4ull * P)) != RT_OK) return s;
+    }
+    if ((s = ensure(c, c->partial, plan.partial_bytes)) != RT_OK) return s;
+    c->last.passes += plan.passes;
+    c->last.partial_bytes = plan.partial_bytes;
+    const size_t pixmap_bytes = c->pixmap.bytes;
+    if ((s = ensure(c, c->pixmap, 4ull * npix)) != RT_OK) return s;
+    if (c->pixmap.bytes != pixmap_bytes) c->tiles_dev.clear();  // reallocated: the old map is gone
+    if ((s = ensure(c, c->blk, 4ull * (nblk_max + 2))) != RT_OK) return s;
+    const bool same_tiles = c->pixmap_for == c->pixmap.ptr && c->pixmap_npix == npix && c->tiles_dev.size() == tl.size() &&
+                            std::memcmp(c->tiles_dev.data(), tl.data(), sizeof(uint4) * tl.size()) == 0;
+    if (!same_tiles) {  // the pixel map of an unchanged tile list is still in pixmap
+      if ((s = ensure(c, c->tiles, sizeof(uint4) * tl.size())) != RT_OK) return s;
+      c->tiles_dev = tl;  // the copy's source outlives this call
+      c->pixmap_for = c->pixmap.ptr;
+      c->pixmap_npix = npix;
+      RT_HIP(c, hipMemcpyAsync(c->tiles.ptr, c->tiles_dev.data(), sizeof(uint4) * tl.size(), hipMemcpyHostToDevice,
+                               st));
+      launch_pixmap((const uint4*)c->tiles.ptr, (uint32_t)tl.size(), npix, (uint32_t*)c->pixmap.ptr, st);
+    }
+
+    unsigned char* sp = (unsigned char*)c->state.ptr;
+    LaunchParams<R> p{};
+    p.sc = dev_scene<R>(hdr, sbase);
+    const uint32_t wide_need = hdr.wide_stack;
+    constexpr uint32_t kWideLdsStack = wide_lds_stack<R>();
+    if (hdr.has_wide && wide_need > kWideLdsStack) {
+      // a deep wide tree: a spill area of (need - kWideLdsStack) entries for every lane the chip can hold
+      int ncu = 0;
+      RT_HIP(c, hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->device));
+      const uint32_t lanes = (uint32_t)std::max(ncu, 1) * 2048u;  // 32 waves of 64 per CU at most
+      if ((s = ensure(c, c->wide_spill, 4ull * (wide_need - kWideLdsStack) * lanes)) != RT_OK) return s;
+      p.sc.wide_spill = (uint32_t*)c->wide_spill.ptr;
+      p.sc.spill_lanes = lanes;
+    }
+    if (prm->traversal == RT_TRAV_ORDERED) p.sc.has_flat = p.sc.has_wide = 0;
+    p.sc.cam64 = nullptr;  // set with the camera below (perspective only)
+    p.O = (R4<R>*)sp;
+    p.D = (R4<R>*)(sp + r4);
+    p.T = (R4<R>*)(sp + 2 * r4);
+    p.L = (R4<R>*)(sp + 3 * r4);
+    p.A = (R4<R>*)(sp + 4 * r4);
+    p.S = (uint4*)(sp + 5 * r4);
+    p.X = (uint4*)(sp + 5 * r4 + sb);
+    p.partial = (R*)c->partial.ptr;
+    p.pixmap = (const uint32_t*)c->pixmap.ptr;
+    p.queue = nullptr;
+    p.n = P;
+    p.P = P;
+    p.npix = npix;
+    div_magic(npix, p.npix_m, p.npix_k);
+    p.n_items = n_items;
+    p.chunk = plan.chunk;
+    p.k_bulk = plan.k_bulk;
+    p.tail_chunk = plan.tail_chunk;
+    p.spp = spp;
+    p.first_sample = (uint32_t)std::max(0, prm->first_sample);
+    p.W = (uint32_t)cam->image_width;
+    p.max_depth = prm->max_depth;
+    p.seed = prm->seed;
+    c->cam_host = make_view(cam);
+    if ((s = ensure(c, c->camx, sizeof(CamDev))) != RT_OK) return s;
+    if (!c->cam_valid || std::memcmp(&c->cam_dev, &c->cam_host, sizeof(CamDev)) != 0) {
+      RT_HIP(c, hipMemcpyAsync(c->camx.ptr, &c->cam_host, sizeof(CamDev), hipMemcpyHostToDevice, st));
+      c->cam_dev = c->cam_host;
+      c->cam_valid = true;
+    }
+    p.cam_mode = c->cam_host.mode;
+    p.camx = (const CamDev*)c->camx.ptr;
+    if (p.cam_mode == RT_CAM_PERSPECTIVE) p.sc.cam64 = p.camx;
+    p.seg_shards = (unsigned long long*)c->counters.ptr;
+    p.K = prm->segments_per_launch > 0 ? std::min(prm->segments_per_launch, 64) : kAutoSegments;
+    if (c->timing && c->ev_used > 4096 && (s = settle(c)) != RT_OK) return s;  // bound the pending events
+    if (persist) {
+      if ((s = ensure(c, c->fault, 4)) != RT_OK) return s;
+      p.persist = kPersist;
+      p.fault = (uint32_t*)c->fault.ptr;
+      if ((s = ensure(c, c->heads, 4ull * kHeads * kHeadStride)) != RT_OK) return s;
+      p.heads = (uint32_t*)c->heads.ptr;
+    }
+    for (uint32_t c0 = 0; c0 < plan.nchunks; c0 += plan.cpp) {  // the passes (one for every BASELINE config but C5)
+      const uint32_t pc = std::min(plan.cpp, plan.nchunks - c0);
+      p.chunk0 = c0;
+      p.n_items = npix * pc;
+      s = persist ? run_persistent(c, p, kind, nblk_max, st) : run_wavefront(c, p, kind, nblk_max, st);
+      if (s != RT_OK) return s;
+      launch_resolve<R>((const R*)c->partial.ptr, npix, pc, spp, (R*)dout, c0 == 0, c0 + pc >= plan.nchunks, st);
+      c->last.launches++;
+      RT_HIP(c, hipGetLastError());
+    }
+    // device output: nothing waits here -- the segment counters (cumulative on the device), the
+    // timing events and the fault word are settled by rt_stats, rt_reset_counters or a host-output call
+    c->pending = true;
+    c->pend_stream = st;
+    c->last.samples += (uint64_t)npix * spp;
+  }
+  if (!out_dev) {
+    RT_HIP(c, hipMemcpyAsync(out, dout, out_elems * sizeof(R), hipMemcpyDeviceToHost, st));
+    RT_HIP(c, hipStreamSynchronize(st));
+    if ((s = settle(c)) != RT_OK) return s;
+  }
+  c->last.last_render_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return RT_OK;
+}
+
+}  // namespace
+
+// ====================================================================== C ABI
+
+extern "C" {
+
+int32_t rt_abi_version(void) { return RT_ABI_VERSION; }
+
+#define RT_STR2(x) #x
+#define RT_STR(x) RT_STR2(x)
+const char* rt_build_info(void) {
+  return "dev_only=" RT_STR(RT_DEV_ONLY) " wide_top_n=" RT_STR(RT_WIDE_TOP_N) " wide_lds_stack=" RT_STR(RT_WIDE_LDS_STACK) " wide_waves_global=" RT_STR(RT_WIDE_WAVES_GLOBAL)
+#ifdef RT_SECTION_CLOCKS
+      " sections=1"
+#endif
+#ifdef RT_DEBUG_TRACE
+      " trace=1"
+#endif
+#ifdef RT_PRECISE_F32
+      " precise_f32=1"
+#endif
+      ;
+}
+#undef RT_STR
+#undef RT_STR2
+
+rt_status rt_context_create(int32_t device, rt_context** out) {
+  if (!out) return set_err(nullptr, RT_ERR_INVALID_ARGUMENT, "out is null");
+  *out = nullptr;
+  int n = 0;
+  hipError_t e = hipGetDeviceCount(&n);
+  if (e != hipSuccess || n == 0) {
+    (void)hipGetLastError();
+    return set_err(nullptr, RT_ERR_NO_DEVICE, std::string("no HIP device: ") + hipGetErrorString(e));
+  }
+  if (device < 0 || device >= n) return set_err(nullptr, RT_ERR_INVALID_ARGUMENT, "device index out of range");
+  if ((e = hipSetDevice(device)) != hipSuccess) return set_err(nullptr, RT_ERR_HIP, hipGetErrorString(e));
+  if ((e = upload_sincos_table()) != hipSuccess)
+    return set_err(nullptr, RT_ERR_HIP, std::string("sin/cos table: ") + hipGetErrorString(e));
+  auto* c = new rt_context;
+  c->device = device;
+  if ((e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)) != hipSuccess) {
+    delete c;
+    return set_err(nullptr, RT_ERR_HIP, hipGetErrorString(e));
+  }
+  if ((e = hipHostMalloc((void**)&c->total_host, 64 + 8 * kSegShards, hipHostMallocDefault)) != hipSuccess) {
+    (void)hipStreamDestroy(c->stream);
+    delete c;
+    return set_err(nullptr, RT_ERR_HIP, hipGetErrorString(e));
+  }
+  if (ensure(c, c->counters, sizeof(unsigned long long) * kSegShards) != RT_OK || ensure(c, c->fault, 4) != RT_OK ||
+      hipMemset(c->counters.ptr, 0, sizeof(unsigned long long) * kSegShards) != hipSuccess ||
+      hipMemset(c->fault.ptr, 0, 4) != hipSuccess) {
+    std::string m = c->err;
+    rt_context_destroy(c);
+    return set_err(nullptr, RT_ERR_OUT_OF_MEMORY, m);
+  }
+  *out = c;
+  return RT_OK;
+}
+
+void rt_context_destroy(rt_context* c) {
+  if (!c) return;
+  (void)hipSetDevice(c->device);
+  // an outstanding device-output render still reads the buffers freed below (its fault word is
+  // dropped with the context: nobody is left to report it to)
+  if (c->pending) (void)hipStreamSynchronize(c->pend_stream);
+  if (c->stream) (void)hipStreamSynchronize(c->stream);
+  for (DevBuf* b : {&c->scene32, &c->scene64, &c->state, &c->partial, &c->pixmap, &c->queue0, &c->queue1, &c->blk, &c->wide_spill,
+                    &c->out_tmp, &c->counters, &c->camx, &c->heads, &c->tiles, &c->fault})
+    if (b->ptr) (void)hipFree(b->ptr);
+  for (hipEvent_t e : c->events) (void)hipEventDestroy(e);
+  if (c->total_host) (void)hipHostFree(c->total_host);
+  if (c->stream) (void)hipStreamDestroy(c->stream);
+  delete c;
+}
+
+const char* rt_last_error(const rt_context* c) {
+  if (c) return c->err.c_str();
+  std::lock_guard<std::mutex> lk(g_err_mu);
+  return g_create_err.c_str();
+}
+
+rt_status rt_scene_upload(rt_context* c, const rt_scene_desc* desc) {
+  if (!c || !desc) return set_err(c, RT_ERR_INVALID_ARGUMENT, "null context or descriptor");
+  RT_HIP(c, hipSetDevice(c->device));
+  CompiledScene cs;
+  std::string err;
+  rt_status s = compile_scene(desc, &cs, &err);
+  if (s != RT_OK) return set_err(c, s, err);
+  // renders still pending on any stream read the current scene buffers
+  if (c->pending) RT_HIP(c, hipStreamSynchronize(c->pend_stream));
+  if ((s = ensure(c, c->scene32, cs.blob32.size())) != RT_OK) return s;
+  if ((s = ensure(c, c->scene64, cs.blob64.size())) != RT_OK) return s;
+  c->scene = std::move(cs);  // copied to the device by the next render, on its stream (render<R>)
+  c->scene_dirty32 = c->scene_dirty64 = true;
+  c->has_scene = true;
+  return RT_OK;
+}
+
+rt_status rt_scene_check(const rt_scene_desc* desc, rt_scene_info* info, char* err, int32_t errlen) {
+  CompiledScene cs;
+  std::string m;
+  rt_status s = desc ? compile_scene(desc, &cs, &m) : RT_ERR_INVALID_ARGUMENT;
+  if (!desc) m = "null descriptor";
+  if (s == RT_OK) {  // the kernels a perspective render on the default (persistent) schedule would take
+    const KernelFamily fam = kernel_family(cs.hdr, RT_CAM_PERSPECTIVE, true, false);
+    if (!family_built(fam)) {
+      s = RT_ERR_UNSUPPORTED;
+      m = std::string("this build (RT_DEV_ONLY) has no ") + family_name(fam) + " kernels";
+    }
+  }
+  if (err && errlen > 0) std::snprintf(err, (size_t)errlen, "%s", m.c_str());
+  if (s == RT_OK && info) {
+    const SceneHeader& h = cs.hdr;
+    info->quads = cs.desc_quads;
+    info->flat_quads = cs.flat_quads;
+    info->flat_boxes = cs.flat_boxes;
+    info->wide_nodes = cs.hdr.has_wide ? (int32_t)cs.hdr.n_wnodes : 0;
+    info->wide_stack = cs.hdr.has_wide ? (int32_t)cs.hdr.wide_stack : 0;
+    info->wide_kinds = cs.hdr.has_wide ? (int32_t)cs.hdr.wide_kinds : 0;
+    info->wide_prim_words = cs.hdr.has_wide ? (int32_t)cs.hdr.n_wprim_words : 0;
+    info->wide_big = cs.hdr.has_wide ? (int32_t)cs.hdr.wide_big : 0;
+    info->spheres = (int32_t)h.n_spheres;
+    info->triangles = (int32_t)h.n_tris;
+    info->instances = h.num_instances;
+    info->volumes = (int32_t)h.n_volumes;
+    info->bvh_nodes = (int32_t)h.n_nodes;
+    info->linear_ops = (int32_t)h.n_linear;
+    info->stack_need = cs.stack_need;
+    info->bytes_f32 = cs.blob32.size();
+    info->bytes_f64 = cs.blob64.size();
+  }
+  return s;
+}
+
+rt_status rt_render_tiles(rt_context* c, const rt_camera_desc* cam, const rt_render_params* prm, const rt_tile* tiles,
+                          int32_t ntiles, void* out_rgb, int32_t out_is_device, void* stream) {
+  if (!c) return set_err(nullptr, RT_ERR_INVALID_ARGUMENT, "null context");
+  if (!cam || !prm || (!tiles && ntiles > 0) || ntiles < 0 || (!out_rgb && ntiles > 0))
+    return set_err(c, RT_ERR_INVALID_ARGUMENT, "null argument");
+  if (!c->has_scene) return set_err(c, RT_ERR_NO_SCENE, "rt_scene_upload has not succeeded on this context");
+  if (cam->mode < RT_CAM_PERSPECTIVE || cam->mode > RT_CAM_LENS)
+    return set_err(c, RT_ERR_INVALID_ARGUMENT, "unknown camera mode");
+  if (cam->image_width <= 0 || cam->image_height <= 0) return set_err(c, RT_ERR_INVALID_ARGUMENT, "empty image");
+  if (cam->image_width > 65535 || cam->image_height > 65535)  // pixel positions are packed x | y << 16
+    return set_err(c, RT_ERR_INVALID_ARGUMENT, "image wider or taller than 65535 pixels");
+  if (prm->spp <= 0) return set_err(c, RT_ERR_INVALID_ARGUMENT, "spp must be positive");
+  if (prm->precision != RT_PREC_F32 && prm->precision != RT_PREC_F64)
+    return set_err(c, RT_ERR_INVALID_ARGUMENT, "unknown precision");
+  for (int t = 0; t < ntiles; t++) {
+    const rt_tile& tl = tiles[t];
+    if (tl.x0 < 0 || tl.y0 < 0 || tl.width < 0 || tl.height < 0 || tl.x0 + tl.width > cam->image_width ||
+        tl.y0 + tl.height > cam->image_height)
+      return set_err(c, RT_ERR_INVALID_ARGUMENT, "tile " + std::to_string(t) + " outside the image");
+  }
+  RT_HIP(c, hipSetDevice(c->device));
+  // Device output: NULL is the HIP null stream (torch's default stream), so work the caller queues
+  // after this call on that stream -- a clone, a gather -- is ordered after the render. Host output
+  // (the call returns the finished image): NULL is the context's own non-blocking stream, so contexts
+  // driven from different host threads do not serialise on the null stream.
+  hipStream_t st = (stream == nullptr && !out_is_device) ? c->stream : (hipStream_t)stream;
+  try {
+    if (prm->precision == RT_PREC_F64) return render<double>(c, cam, prm, tiles, ntiles, out_rgb, out_is_device, st);
+    return render<float>(c, cam, prm, tiles, ntiles, out_rgb, out_is_device, st);
+  } catch (const std::bad_alloc&) {
+    return set_err(c, RT_ERR_OUT_OF_MEMORY, "out of host memory");
+  } catch (const std::exception& e) {
+    return set_err(c, RT_ERR_INVALID_ARGUMENT, e.what());
+  }
+}
+
+rt_status rt_stats(rt_context* c, rt_counters* out) {
+  if (!c || !out) return set_err(c, RT_ERR_INVALID_ARGUMENT, "null argument");
+  RT_HIP(c, hipSetDevice(c->device));
+  const rt_status s = settle(c);
+  *out = c->last;
+  return s;
+}
+
+rt_status rt_reset_counters(rt_context* c) {
+  if (!c) return set_err(nullptr, RT_ERR_INVALID_ARGUMENT, "null context");
+  RT_HIP(c, hipSetDevice(c->device));
+  const rt_status s = settle(c);  // nothing of this context is outstanding after it
+  RT_HIP(c, hipMemsetAsync(c->counters.ptr, 0, sizeof(unsigned long long) * kSegShards, c->stream));
+  if (c->fault.ptr) RT_HIP(c, hipMemsetAsync(c->fault.ptr, 0, 4, c->stream));
+  RT_HIP(c, hipStreamSynchronize(c->stream));
+  c->last = rt_counters{};
+  return s;
+}
+
+rt_status rt_set_timing(rt_context* c, int32_t enable) {
+  if (!c) return set_err(nullptr, RT_ERR_INVALID_ARGUMENT, "null context");
+  c->timing = enable ? 1 : 0;
+  return RT_OK;
+}
+
+uint32_t rt_rng_u32(uint64_t seed, uint32_t pixel, uint32_t sample, uint32_t dim) {
+  return draw_u32(key_path(key_pixel(seed, pixel), key_sample(seed, sample)), dim);
+}
+
+}  // extern "C"

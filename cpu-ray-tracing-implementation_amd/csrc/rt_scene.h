@@ -19,6 +19,12 @@
 
 #include <stdint.h>
 
+// a plain C++ compiler (the host-only users: rt_plan.h's test program) knows no function qualifiers
+#if !defined(__HIP__) && !defined(__host__)
+#define __host__
+#define __device__
+#endif
+
 namespace rtd {
 
 enum : uint32_t {

@@ -1,6 +1,6 @@
 #!/bin/bash
 # GPU box, development: C1 (a small frame) against the work-item size -- explicit --chunk values, and the
-# automatic size under RT_ITEMS_TARGET (items the frame should have at least; rt_kernels.hip render())
+# automatic size under RT_ITEMS_TARGET (items the frame should have at least; rt_plan.h plan_items)
 mkdir -p gpurun_out/r04x
 run() {  # <tag> <precision> [bench args...]
   local tag=$1 prec=$2; shift 2

@@ -28,8 +28,8 @@ for name, want in (("cornell_box", abi.RT_OK), ("rtow", abi.RT_ERR_UNSUPPORTED),
 '''
 
 
-SRCS = ("rt_kernels.hip", "rt_multi.hip", "scene_compile.cpp", "rt_device.h", "rt_scene.h", "rt_sin.h",
-        "scene_compile.h")
+SRCS = ("rt_kernels.hip", "rt_render.hip", "rt_multi.hip", "scene_compile.cpp", "rt_device.h", "rt_types.h",
+        "rt_launch.h", "rt_plan.h", "rt_scene.h", "rt_sin.h", "scene_compile.h")
 
 
 def dev_build():
@@ -47,7 +47,7 @@ def dev_build():
             os.remove(os.path.join(cache, old))
         tmp = lib + ".tmp"
         cmd = [HIPCC, "-O1", "-std=c++17", "-fPIC", "-ffp-contract=on", "-fno-slp-vectorize", "--offload-arch=gfx950",
-               "-DRT_DEV_ONLY=1", "-shared", "-o", tmp] + [os.path.join(CSRC, f) for f in SRCS[:3]] + ["-ldl"]
+               "-DRT_DEV_ONLY=1", "-shared", "-o", tmp] + [os.path.join(CSRC, f) for f in SRCS[:4]] + ["-ldl"]
         subprocess.run(cmd, check=True, timeout=600)
         os.replace(tmp, lib)
     return lib

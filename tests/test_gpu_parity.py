@@ -547,7 +547,7 @@ def test_c1_full_frame_matches_oracle(ctx):
 def test_c5_full_width_rows_at_4096_spp_match_oracle(ctx):
     # BASELINE config 5 (main.cc:227-253: Cornell box with two volumne.h smoke boxes, MIS light pdf) at its
     # own 3840x2160, 4096 spp, depth 5: three full-width rows through the smoke boxes, rendered as tiles of
-    # the full frame. 4096 spp takes the item-layout doubling (rt_kernels.hip render(): at most 256 items
+    # the full frame. 4096 spp takes the item-layout doubling (rt_plan.h plan_items: at most 256 items
     # per pixel, so bulk and tail items double to 32 / 16 samples), which smaller tests never reach.
     cs = plugin.ConfigScene("cornell_box_with_volume", 3840, 16.0 / 9.0)
     W, H = cs.cam.image_width, cs.cam.image_height

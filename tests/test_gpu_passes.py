@@ -1,4 +1,4 @@
-"""Renders whose item partial sums exceed the memory budget come in chunk passes (rt_kernels.hip render(),
+"""Renders whose item partial sums exceed the memory budget come in chunk passes (rt_plan.h plan_items,
 k_resolve): every pass is one launch over a range of each pixel's chunks, and its resolve adds them to the
 running per-pixel sums in chunk order -- the additions camera.h:163-170's per-pixel loop makes, in the same
 order as one pass. So the image must be bit-identical whatever the budget, and a call past 2^31 items (which
