@@ -492,6 +492,13 @@ __device__ bool shade(const Params<R>& p, PS& s, R t, uint32_t e, int32_t inst, 
   bool has_add = false, done = false;
   V<R> new_o = s.o, new_d = s.d;
   const V<R> o = s.o, d = s.d;
+  // The fp64 flat LL kernel (round 7) updates the path state in place: the scatter writes the next ray into s and
+  // returns from there, and every other lane -- its sample is finished -- goes on to begin_sample, which writes the
+  // whole state. No lane then leaves shade with the origin, direction and throughput it entered with, and the
+  // compiler keeps fewer copies of them: through new_o / new_d and the common `!done` exit below, every join of the
+  // segment loop copied the nine values from one set of registers to another (C2 fp64 25.29 -> 24.49 ms/frame; the
+  // fp32 twin lost, 18.34 -> 18.57, and keeps the code it had, as every other kernel).
+  constexpr bool kInPlace = FLAT && LL && sizeof(R) == 8;
 
   if (e == kNoHit) {  // camera::miss (camera.h:180-190)
 #ifdef RT_DEBUG_TRACE
@@ -795,6 +802,16 @@ __device__ bool shade(const Params<R>& p, PS& s, R t, uint32_t e, int32_t inst, 
         const V<R> thr = s.thr();
         if (thr.x == R(0) && thr.y == R(0) && thr.z == R(0)) done = true;
       }
+      if constexpr (kInPlace) {  // (no emission on this branch: nothing below concerns a lane that goes on)
+        s.o = new_o;
+        s.d = new_d;
+        if (!done) {
+          s.bounce += 1;
+          s.xe = e;
+          s.xi = inst;
+          return true;
+        }
+      }
     }
   }
   if (has_add) {
@@ -803,7 +820,7 @@ __device__ bool shade(const Params<R>& p, PS& s, R t, uint32_t e, int32_t inst, 
     else
       s.rad = s.rad + add;
   }
-  if (!done) {
+  if (!kInPlace && !done) {
     s.o = new_o;
     s.d = new_d;
     s.bounce += 1;
@@ -815,6 +832,7 @@ __device__ bool shade(const Params<R>& p, PS& s, R t, uint32_t e, int32_t inst, 
   RT_WIDE_STAT(8);
   V<R> acc = s.acc();
   if constexpr (!PS::kNoRad) acc = acc + s.rad;
+  [[maybe_unused]] bool retire = false;
   const uint32_t sample = s.sample() + 1;
   s.set_sample(sample);
   if (sample < send_of(p, s)) {
@@ -832,15 +850,28 @@ __device__ bool shade(const Params<R>& p, PS& s, R t, uint32_t e, int32_t inst, 
     // persistent schedule: from the wave's queue; wavefront schedule: the slot's next item, P further on
     const uint32_t nx = p.persist == kPersist ? next_item_dyn(p) : (item + p.P < p.n_items ? item + p.P : kNoItem);
     if (nx == kNoItem) {
-      s.bounce = -1;
-      return false;
+      if constexpr (kInPlace) {
+        retire = true;  // (below)
+      } else {
+        s.bounce = -1;
+        return false;
+      }
+    } else {
+      begin_item(p, s, nx);
     }
-    begin_item(p, s, nx);
   }
   // (round 5: regenerating the finished lanes of a wave in batches -- a lane waiting idle until 16 or 32 of
   // its wave's lanes had finished -- was slower, C2 fp64 28.33 -> 28.46 / 29.95 ms/frame, r05e: the lanes a
   // wait idles in trace and shade cost more than the regeneration's 41 % lane use)
   begin_sample<R, CAMX>(p, s);
+  // kInPlace: a retiring lane generated a ray too (of its last item: registers only, never traced), so that it also
+  // leaves with a state written here
+  if constexpr (kInPlace) {
+    if (retire) {
+      s.bounce = -1;
+      return false;
+    }
+  }
   return true;
 }
 
