@@ -9,6 +9,8 @@
 // rebuilding the live-slot queue. k_resolve: the per-pixel mean over the chunks, in chunk order. Each sample's
 // random numbers are keyed by (seed, global pixel, sample), so the image is bit-identical for any pool size,
 // tiling or GPU count. k_trace: closest hits of caller-given rays through the same traversals (rt_trace_rays).
+// k_camera_rays: the rays a render draws (rt_camera_rays); k_aov: per pixel the first-hit albedo, normal, depth and
+// ids over those rays, through k_trace's loop (rt_render_aov).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -1373,9 +1375,11 @@ struct QueryRay {
 // hit_record of the closest hit (t, e, inst, nm) of the ray (o, d, tm): the point, the face-forwarded normal and
 // front_face as shade computes them before it reads the material -- a restatement of shade's geometry block for
 // the base kernels (CAMX = false, MOVING = true), kept apart so that shade's code does not move.
+// obj_n (the feature-buffer pass): where given, the object-space outward normal of a sphere, quad or triangle,
+// before it is face-forwarded and rotated out -- what sphere.h:70 takes u, v from.
 template <class R, bool FLAT>
 __device__ __forceinline__ void hit_record(const DevScene<R>& sc, V<R> o, V<R> d, R tm, R t, uint32_t e, int32_t inst,
-                                           uint32_t nm, V<R>& pw, V<R>& n, bool& front) {
+                                           uint32_t nm, V<R>& pw, V<R>& n, bool& front, V<R>* obj_n = nullptr) {
   const uint32_t ty = etype(e), idx = epay(e);
   if constexpr (FLAT) {  // quad.h:47-50 with n = +-e_A; hit_record::set_face_normal (hittable.h:26-29)
     const uint32_t A = (nm >> 28) & 3u;
@@ -1430,6 +1434,7 @@ __device__ __forceinline__ void hit_record(const DevScene<R>& sc, V<R> o, V<R> d
   } else {
     outward = ld3(sc.tris[idx].n);
   }
+  if (obj_n) *obj_n = outward;
   if (world_space) {  // dd is the world ray: the object-space normal goes out first
     if (in)
       for (int q = in->nops - 1; q >= 0; q--) outward = op_out(in->op[q], outward, false);
@@ -1489,44 +1494,239 @@ __device__ __forceinline__ void store_query(const KTrace<R>& a, uint32_t i, cons
   *(int4*)(a.ids + 4ull * i) = id;
 }
 
-template <class R, class Trav>
-__global__ __launch_bounds__(kBlock) void k_trace(KTrace<R> a) {
+// The loop of the query kernels over a traversal policy, a grid-stride loop over resident lanes. A Job is the ray
+// source and the hit sink: valid() says whether the lane has a first ray, load() builds the current one, hit() takes
+// its closest hit, advance() moves on and says whether there is another. k_trace's job reads caller-given rays and
+// writes one record a ray; k_aov's builds the camera rays of a pixel and sums their feature channels.
+template <class R, class Trav, class Job>
+__device__ __forceinline__ void query_loop(const DevScene<R>& sc, Job& job) {
   __shared__ Lds<Trav::kStack * kBlock> stk;
-  const uint32_t stride = gridDim.x * kBlock;  // at most the resident lanes: i + stride stays below 2^32
-  uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-  if (i == 0) atomicAdd(a.seg_shards, (unsigned long long)a.n);  // rt_counters.segments
   QueryRay<R> s;
-  double tmax;
   if constexpr (Trav::kWide) {
     // the resumable traversal, driven as persist_body drives it: a ray paused with the wave's laggards carries on
     // beside the rays the finished lanes take next
     using StackT = typename Trav::StackT;
     extern __shared__ uint4 dyn_lds[];
-    StackT* wstk = Trav::fill(a.sc, dyn_lds) + threadIdx.x;  // (every lane of the block: it holds the barriers)
-    if (i >= a.n) return;
-    load_query(a, i, s, tmax);
-    const uint32_t root = Trav::root(a.sc);
+    StackT* wstk = Trav::fill(sc, dyn_lds) + threadIdx.x;  // (every lane of the block: it holds the barriers)
+    if (!job.valid()) return;
+    job.load(s);
+    const uint32_t root = Trav::root(sc);
     WideRayT<R> ry{root, 0, Num<R>::inf(), kNoHit, 1u};
 #pragma unroll 1
     for (;;) {
-      if (!Trav::steps(a.sc, (const Node<R>*)dyn_lds, s, wstk, ry)) continue;
-      store_query<R, false>(a, i, s, tmax, ry.tmax, ry.e, -1, 0u);
-      i += stride;
-      if (i >= a.n) break;
-      load_query(a, i, s, tmax);
+      if (!Trav::steps(sc, (const Node<R>*)dyn_lds, s, wstk, ry)) continue;
+      job.template hit<false>(s, ry.tmax, ry.e, -1, 0u);
+      if (!job.advance()) break;
+      job.load(s);
       ry = WideRayT<R>{root, 0, Num<R>::inf(), kNoHit, 1u};
     }
   } else {
 #pragma unroll 1
-    for (; i < a.n; i += stride) {
-      load_query(a, i, s, tmax);
+    for (bool more = job.valid(); more; more = job.advance()) {
+      job.load(s);
       R t;
       uint32_t e, nm = 0;
       int32_t inst;
-      Trav::run(a.sc, a.sc.nodes, s, Keys{s.ks}, stk.v + threadIdx.x, t, e, inst, nm);
-      store_query<R, Trav::kFlat>(a, i, s, tmax, t, e, inst, nm);
+      Trav::run(sc, sc.nodes, s, Keys{s.ks}, stk.v + threadIdx.x, t, e, inst, nm);
+      job.template hit<Trav::kFlat>(s, t, e, inst, nm);
     }
   }
+}
+
+template <class R>
+struct TraceJob {
+  const KTrace<R>& a;
+  uint32_t i, stride;  // stride: at most the resident lanes, so i + stride stays below 2^32
+  double tmax;
+  __device__ __forceinline__ bool valid() const { return i < a.n; }
+  __device__ __forceinline__ void load(QueryRay<R>& s) { load_query(a, i, s, tmax); }
+  template <bool FLAT>
+  __device__ __forceinline__ void hit(const QueryRay<R>& s, R t, uint32_t e, int32_t inst, uint32_t nm) {
+    store_query<R, FLAT>(a, i, s, tmax, t, e, inst, nm);
+  }
+  __device__ __forceinline__ bool advance() {
+    i += stride;
+    return i < a.n;
+  }
+};
+
+template <class R, class Trav>
+__global__ __launch_bounds__(kBlock) void k_trace(KTrace<R> a) {
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  if (i == 0) atomicAdd(a.seg_shards, (unsigned long long)a.n);  // rt_counters.segments
+  TraceJob<R> job{a, i, gridDim.x * kBlock, 0.0};
+  query_loop<R, Trav>(a.sc, job);
+}
+
+// ------------------------------------------------------------------ camera rays and feature buffers
+// camera::generate_ray (camera.h:244-293) for the sample with path key ks of pixel (x, y), every camera model, in
+// fp64: the ray begin_sample builds (its perspective branch and camera_ray, through the same persp_pixel /
+// persp_sample and the same draws), with the camera read as wave-uniform scalars. The one helper of k_camera_rays
+// and k_aov, so the rays the one writes are bit for bit the rays the other traces. EXT = false: the perspective
+// camera only (k_aov's base form, which then calls nothing out of line).
+template <bool EXT>
+__device__ __forceinline__ void sample_ray(const CamDev* cp, int32_t mode, uint32_t ks, uint32_t x, uint32_t y,
+                                           V<double>& o, V<double>& d, double& tm) {
+  const double ox = to_unit<double>(draw_u32(ks, 0)) - 0.5;  // sample_square (camera.h:293)
+  const double oy = to_unit<double>(draw_u32(ks, 1)) - 0.5;
+  if (!EXT || mode == RT_CAM_PERSPECTIVE) {  // camera.h:245-251
+    const V<double> du = ld_uniform(&cp->du, 0), dv = ld_uniform(&cp->dv, 0);
+    o = ld_uniform(&cp->pos, 0);
+    d = persp_sample(persp_pixel(ld_uniform(&cp->dir00, 0), du, dv, x, y), du, dv, ox, oy);
+    tm = to_unit<double>(draw_u32(ks, 2));
+  } else if constexpr (EXT) {
+    camera_ray(cp, ks, x, y, ox, oy, o, d, tm);
+  }
+}
+
+// rt_camera_rays: one lane per (pixel, sample), rows in rt_trace_rays' format
+__global__ __launch_bounds__(kBlock) void k_camera_rays(CamRayParams a) {
+  const uint32_t r = blockIdx.x * kBlock + threadIdx.x;
+  if (r >= a.npix * a.spp) return;
+  const uint32_t pix = r / a.spp, sidx = r - pix * a.spp;
+  const uint32_t xy = a.pixmap[pix], x = xy & 0xFFFFu, y = xy >> 16;
+  const uint32_t ks = key_path(key_pixel(a.seed, y * a.W + x), key_sample(a.seed, a.first_sample + sidx));
+  V<double> o, d;
+  double tm;
+  sample_ray<true>(a.camx, a.cam_mode, ks, x, y, o, d, tm);
+  double2* q = (double2*)(a.rays + 8ull * r);  // 64 bytes, 16-byte aligned
+  q[0] = make_double2(o.x, o.y);
+  q[1] = make_double2(o.z, d.x);
+  q[2] = make_double2(d.y, d.z);
+  q[3] = make_double2(tm, __builtin_huge_val());
+}
+
+// k_aov: the first-hit feature buffers of a frame (rt_render_aov). The work item is a pixel: the lane builds the
+// pixel's camera rays one after the other, traces each through the query loop above and adds its albedo, normal,
+// depth and hit flag to eight double sums, in sample order -- so a pixel's values depend on nothing but (seed,
+// pixel, samples) -- and stores the means once.
+// EXT, as the render kernels' CAMX: the form for a non-perspective camera or a texture other than solid and checker
+// (rt_plan.h aov_extended). The base form holds the perspective camera and tex_sample's solid / checker branch only
+// and calls no out-of-line function of the extended kernels, so it keeps the query kernels' register budget.
+template <class R>
+struct KAov : AovParams<R> {};
+
+template <class R, bool EXT>
+struct AovJob {
+  const KAov<R>& a;
+  uint32_t pix, stride;
+  uint32_t sidx, xy, ka;
+  double dlen;  // |d| of the running sample's fp64 ray: depth = t |d|
+  double ar, ag, ab, nx, ny, nz, depth, hits;
+  int4 id;
+
+  __device__ __forceinline__ void begin_pixel() {
+    xy = a.pixmap[pix];
+    ka = key_pixel(a.seed, (xy >> 16) * a.W + (xy & 0xFFFFu));
+    sidx = 0;
+    ar = ag = ab = nx = ny = nz = depth = hits = 0.0;
+    id = make_int4(-1, -1, -1, -1);
+  }
+  __device__ __forceinline__ bool valid() {
+    if (pix >= a.npix) return false;
+    begin_pixel();
+    return true;
+  }
+  __device__ __forceinline__ void load(QueryRay<R>& s) {
+    s.ks = key_path(ka, key_sample(a.seed, a.first_sample + sidx));  // the pixel's own path key: volume draws too
+    V<double> o, d;
+    double tm;
+    sample_ray<EXT>(a.camx, a.cam_mode, s.ks, xy & 0xFFFFu, xy >> 16, o, d, tm);
+    dlen = sqrt(dot(d, d));
+    s.o = mkv(R(o.x), R(o.y), R(o.z));
+    s.d = mkv(R(d.x), R(d.y), R(d.z));
+    s.tm = R(tm);
+    s.bounce = 0;
+    s.xe = kNoHit;
+    s.xi = -1;
+  }
+  template <bool FLAT>
+  __device__ __forceinline__ void hit(const QueryRay<R>& s, R t, uint32_t e, int32_t inst, uint32_t nm) {
+    const DevScene<R>& sc = a.sc;
+    V<R> alb = mkv(R(0), R(0), R(0));
+    if (e == kNoHit) {  // camera::miss (camera.h:180-190): the background through its unit-sphere test
+      if (sc.background >= 0) {
+        const V<R> o = s.o, d = s.d;
+        R tb;
+        if (sphere_roots<R>(o.x, o.y, o.z, d.x, d.y, d.z, o.x, o.y, o.z, R(1), R(0.001), Num<R>::inf(), false, tb)) {
+          const Texture<R>& bt = sc.texs[sc.background];
+          double bu = 0, bv = 0;
+          if constexpr (EXT)
+            if (bt.kind == T_IMAGE) sphere_uv(tb * d, bu, bv);  // (only a picture reads u, v)
+          alb = tex_sample<R, EXT>(sc, bt, o + tb * d, bu, bv);
+        }
+      }
+    } else {
+      V<R> pw, n, on;
+      bool front;
+      hit_record<R, FLAT>(sc, s.o, s.d, s.tm, t, e, inst, nm, pw, n, front, &on);
+      const uint32_t ty = etype(e), idx = epay(e);
+      int32_t mat;  // the material shade reads for this record
+      if constexpr (FLAT)
+        mat = (int32_t)(nm & kNmMat);
+      else
+        mat = ty == E_VOLUME ? sc.vols[idx].phase_mat
+              : ty == E_QUAD ? sc.quads[idx].mat
+                             : ty == E_SPHERE ? sc.spheres[idx].mat : sc.tris[idx].mat;
+      const Material<R>& m = sc.mats[mat];
+      double hu = 0, hv = 0;  // hit_record u, v as shade's extended branch has them; only a picture reads them
+      if constexpr (EXT && !FLAT) {  // (aov_family: a scene with pictures never takes the flat program)
+        if (m.tx.kind == T_IMAGE) {
+          if (ty == E_QUAD) {  // quad.h:47-62: alpha, beta of the object-space point
+            const Quad<R>& q = sc.quads[idx];
+            V<R> oo = s.o, dd = s.d;
+            if (inst >= 0) chain_in(sc.insts[inst], oo, dd);
+            const V<R> rel = (oo + t * dd) - ld3(q.q);
+            hu = (double)dot(rel, ld3(q.a));
+            hv = (double)dot(rel, ld3(q.b));
+          } else if (ty == E_SPHERE) {
+            sphere_uv(on, hu, hv);  // sphere.h:70
+          }
+        }
+      }
+      alb = tex_sample<R, EXT>(sc, m.tx, pw, hu, hv);
+      nx += (double)n.x;
+      ny += (double)n.y;
+      nz += (double)n.z;
+      depth += (double)t * dlen;
+      hits += 1.0;
+      if (sidx == 0) {  // the ids of sample first_sample, as store_query reports them
+        const uint32_t tab = ty == E_VOLUME ? 3u : ty;
+        const int2 om = a.idtab[a.id_off[tab] + idx];
+        const int32_t kind = ty == E_QUAD ? RT_OBJ_QUAD : ty == E_SPHERE ? RT_OBJ_SPHERE : ty == E_TRI ? RT_OBJ_TRIANGLE : RT_OBJ_VOLUME;
+        id = make_int4(om.x, om.y, kind, front ? 1 : 0);
+      }
+    }
+    ar += (double)alb.x;
+    ag += (double)alb.y;
+    ab += (double)alb.z;
+  }
+  __device__ __forceinline__ bool advance() {
+    if (++sidx < a.spp) return true;
+    const double n = (double)a.spp;
+    double2* f = (double2*)(a.feat + 8ull * pix);  // 64 bytes, 16-byte aligned
+    f[0] = make_double2(ar / n, ag / n);
+    f[1] = make_double2(ab / n, nx / n);
+    f[2] = make_double2(ny / n, nz / n);
+    f[3] = make_double2(depth / n, hits / n);
+    *(int4*)(a.ids + 4ull * pix) = id;
+    pix += stride;  // at most the resident lanes: pix + stride stays below 2^32
+    if (pix >= a.npix) return false;
+    begin_pixel();
+    return true;
+  }
+};
+
+// waves per SIMD of the extended form: the extended render kernels' (RT_CAMX_W). It calls the same out-of-line functions they call
+// (camera_ray, sphere_uv, the noise textures), and the compiler gives such a function the loosest register budget of
+// its callers: without the attribute those functions grow to 248 VGPRs and every extended render kernel, which
+// counts its callees' registers, falls to one wave per SIMD.
+template <class R, class Trav, bool EXT>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(EXT ? RT_CAMX_W(R) : 1))) void k_aov(KAov<R> a) {
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  if (i == 0) atomicAdd(a.seg_shards, (unsigned long long)a.npix * a.spp);  // rt_counters.segments
+  AovJob<R, EXT> job{a, i, gridDim.x * kBlock};
+  query_loop<R, Trav>(a.sc, job);
 }
 
 // ------------------------------------------------------------------ live-slot compaction
@@ -1771,15 +1971,26 @@ void launch_k(const Params<R>& p, uint32_t grid, hipStream_t st) {
   }
 }
 
-// One k_trace launch: a block per 256 rays, at most what the chip holds resident of this kernel and `max_blocks`
-template <class R, class Trav>
-void launch_trace_k(const KTrace<R>& p, uint32_t max_blocks, hipStream_t st, size_t lds = 0) {
-  auto kern = k_trace<R, Trav>;
+// One launch of a query kernel over n work items (k_trace: rays, k_aov: pixels): a block per 256 of them, at most what
+// the chip holds resident of this kernel and `max_blocks`
+template <class KernelT, class P>
+void launch_resident(KernelT kern, const P& p, uint32_t n, uint32_t max_blocks, hipStream_t st, size_t lds) {
   int dev = 0;
   const uint32_t res = hipGetDevice(&dev) == hipSuccess ? resident_blocks((const void*)kern, dev, lds) : 0;
-  uint32_t grid = std::min<uint32_t>((p.n + kBlock - 1) / kBlock, max_blocks);
+  uint32_t grid = std::min<uint32_t>((n + kBlock - 1) / kBlock, max_blocks);
   if (res > 0) grid = std::min(grid, res);
   hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), lds, st, p);
+}
+template <class R, class Trav>
+void launch_trace_k(const KTrace<R>& p, uint32_t max_blocks, hipStream_t st, size_t lds = 0) {
+  launch_resident(k_trace<R, Trav>, p, p.n, max_blocks, st, lds);
+}
+template <class R, class Trav>
+void launch_aov_k(const KAov<R>& p, uint32_t max_blocks, hipStream_t st, size_t lds = 0) {
+  if (p.ext)
+    launch_resident(k_aov<R, Trav, true>, p, p.npix, max_blocks, st, lds);
+  else
+    launch_resident(k_aov<R, Trav, false>, p, p.npix, max_blocks, st, lds);
 }
 
 }  // namespace
@@ -1877,6 +2088,38 @@ void launch_trace(const TraceParams<R>& tp, TraceFamily fam, hipStream_t st) {
   }
 }
 
+// The feature-buffer pass: the same instantiations (each in its base and its extended form), a lane per pixel
+template <class R>
+void launch_aov(const AovParams<R>& ap, TraceFamily fam, hipStream_t st) {
+  const KAov<R> p{ap};
+  constexpr uint32_t kMaxBlocks = 1u << 14;
+  switch (fam) {
+    case TF_FLAT:
+      if constexpr (family_built(KF_FLAT)) launch_aov_k<R, FlatTrav<R>>(p, kMaxBlocks, st);
+      return;
+    case TF_LINEAR:
+      if constexpr (family_built(KF_LIN_ALL)) launch_aov_k<R, LinearTrav<R, true, true, true>>(p, kMaxBlocks, st);
+      return;
+    case TF_WIDE_LDS:
+      if constexpr (family_built(KF_WIDE))
+        launch_aov_k<R, WideTrav<R, true, true, true, true, true>>(p, kMaxBlocks, st, wide_lds_bytes(p.sc, true));
+      return;
+    case TF_WIDE_HBM:
+      if constexpr (family_built(KF_WIDE))  // the spill area holds spill_lanes lanes: never launch more
+        launch_aov_k<R, WideTrav<R, true, true, true, true, false>>(
+            p, p.sc.wide_spill ? std::min<uint32_t>(kMaxBlocks, p.sc.spill_lanes / kBlock) : kMaxBlocks, st,
+            wide_lds_bytes(p.sc, false));
+      return;
+    case TF_STACK:
+      if constexpr (family_built(KF_STACK)) launch_aov_k<R, StackTrav<R, kStackDepth>>(p, kMaxBlocks, st);
+      return;
+  }
+}
+void launch_camera_rays(const CamRayParams& p, hipStream_t st) {
+  const uint32_t n = p.npix * p.spp;
+  hipLaunchKernelGGL(k_camera_rays, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, p);
+}
+
 template <class R>
 void launch_init(const LaunchParams<R>& lp, uint32_t blocks, hipStream_t st) {
   const Params<R> p{lp};
@@ -1914,6 +2157,7 @@ void launch_pixmap(const uint4* tiles, uint32_t ntiles, uint32_t npix, uint32_t*
   template void launch_step<R>(const LaunchParams<R>&, KernelFamily, bool, bool, bool, int, uint32_t, hipStream_t); \
   template void launch_init<R>(const LaunchParams<R>&, uint32_t, hipStream_t);                                   \
   template void launch_trace<R>(const TraceParams<R>&, TraceFamily, hipStream_t);                                \
+  template void launch_aov<R>(const AovParams<R>&, TraceFamily, hipStream_t);                                    \
   template void launch_resolve<R>(const R*, uint32_t, uint32_t, uint32_t, R*, bool, bool, hipStream_t);
 RT_INSTANTIATE(double)
 RT_INSTANTIATE(float)

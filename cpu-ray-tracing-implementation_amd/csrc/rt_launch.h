@@ -136,6 +136,41 @@ struct TraceParams {
 template <class R>
 void launch_trace(const TraceParams<R>& p, TraceFamily fam, hipStream_t st);
 
+// ---- feature buffers (rt_render_aov) and camera rays (rt_camera_rays). Their own kernargs, for the reason above.
+//   pixmap  local pixel -> x | y << 16 (launch_pixmap), camx the camera view (make_view) in device memory
+//   feat  [npix][8] doubles  albedo, normal, depth, hit: the means over the pixel's samples (four 16-byte stores)
+//   ids   [npix][4] int32    object, material, kind, front of sample first_sample
+template <class R>
+struct AovParams {
+  DevScene<R> sc;  // cam64 = nullptr, as a query's: the lane's ray is the fp64 camera ray rounded once
+  const uint32_t* pixmap;
+  const CamDev* camx;
+  double* feat;
+  int32_t* ids;
+  const int2* idtab;
+  uint32_t id_off[4];
+  uint32_t npix, spp, first_sample, W;
+  int32_t cam_mode;
+  int32_t ext;  // aov_extended (rt_plan.h): the kernel form with every camera model and texture kind
+  uint64_t seed;
+  unsigned long long* seg_shards;  // [0] += npix * spp
+};
+// One feature-buffer launch of family `fam` (aov_family; built: family_built(trace_render_family(fam))): a lane per
+// pixel, striding over the pixels when the chip (or the wide spill area) holds fewer lanes.
+template <class R>
+void launch_aov(const AovParams<R>& p, TraceFamily fam, hipStream_t st);
+
+//   rays  [npix * spp][8] doubles  o, d, time, +inf: row pix * spp + s is sample first_sample + s of pixel pix
+struct CamRayParams {
+  const uint32_t* pixmap;
+  const CamDev* camx;
+  double* rays;
+  uint32_t npix, spp, first_sample, W;  // npix * spp < 2^31
+  int32_t cam_mode;
+  uint64_t seed;
+};
+void launch_camera_rays(const CamRayParams& p, hipStream_t st);
+
 // the fp64 sin/cos table (rt_device.h g_sincos_tab) copied to the calling thread's device
 hipError_t upload_sincos_table();
 

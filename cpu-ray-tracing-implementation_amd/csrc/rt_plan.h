@@ -68,6 +68,19 @@ inline TraceFamily trace_family(const SceneHeader& h, bool ordered, size_t word_
     return wide_tree_in_lds(h.n_wnodes, h.n_wprim_words, h.wide_stack, word_bytes) ? TF_WIDE_LDS : TF_WIDE_HBM;
   return TF_STACK;
 }
+// The traversal the feature-buffer pass (rt_render_aov) takes: the query's, with one exception. The pass samples the
+// hit material's texture, and a picture texture needs the hit's u, v; the flat program's record (a face's axis, sign
+// and material) cannot supply them, so a scene with an RT_TEX_IMAGE texture leaves the flat program for the next
+// family in trace_family's order (a flat-eligible scene always has a linear program).
+inline TraceFamily aov_family(const SceneHeader& h, bool ordered, size_t word_bytes) {
+  const bool pictures = (h.tex_kinds & (1u << T_IMAGE)) != 0;
+  return trace_family(h, ordered || (pictures && h.has_flat), word_bytes);
+}
+// Whether the pass needs its kernel's extended form: a camera model other than the perspective one, or a texture
+// other than solid and checker (the base form's tex_sample holds those two only).
+inline bool aov_extended(const SceneHeader& h, int32_t cam_mode) {
+  return cam_mode != RT_CAM_PERSPECTIVE || (h.tex_kinds & ~((1u << T_SOLID) | (1u << T_CHECKER))) != 0;
+}
 // the render family whose RT_DEV_ONLY switch decides whether a build has the query kernel of `f`
 inline KernelFamily trace_render_family(TraceFamily f) {
   return f == TF_FLAT ? KF_FLAT : f == TF_LINEAR ? KF_LIN_ALL : f == TF_STACK ? KF_STACK : KF_WIDE;

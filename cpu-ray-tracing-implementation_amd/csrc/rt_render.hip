@@ -1,5 +1,5 @@
 // rt_render.hip -- the host side of librt_hip.so: contexts and their device buffers, render<R>() and its two
-// schedules, trace_rays<R>() (ray queries), and the C ABI of include/rt_hip.h. It contains no kernel: what a render launches goes through
+// schedules, trace_rays<R>() (ray queries), camera_rays() and render_aov<R>() (feature buffers), and the C ABI of include/rt_hip.h. It contains no kernel: what a render launches goes through
 // rt_launch.h (rt_kernels.hip), and its item layout and kernel family come from rt_plan.h.
 #include <hip/hip_runtime.h>
 
@@ -341,6 +341,53 @@ rt_status run_wavefront(rt_context* c, LaunchParams<R> p, const StepKind& k, uin
   }
 }
 
+// The tile list of a call as k_pixmap takes it: {x0, y0, width, first packed pixel} of every tile that is not
+// empty, in the given order; npix: the pixels of all of them.
+std::vector<uint4> pack_tiles(const rt_tile* tiles, int32_t ntiles, uint64_t& npix) {
+  std::vector<uint4> tl;
+  tl.reserve(ntiles);
+  npix = 0;
+  for (int t = 0; t < ntiles; t++) {
+    if (tiles[t].width == 0 || tiles[t].height == 0) continue;
+    tl.push_back(make_uint4((uint32_t)tiles[t].x0, (uint32_t)tiles[t].y0, (uint32_t)tiles[t].width, (uint32_t)npix));
+    npix += (uint64_t)tiles[t].width * (uint64_t)tiles[t].height;
+  }
+  return tl;
+}
+
+// The pixel map of the tile list in c->pixmap (tiles packed in order, row-major inside each tile), expanded by
+// k_pixmap on `st` unless the map of the same list is still there.
+rt_status pixel_map(rt_context* c, const std::vector<uint4>& tl, uint32_t npix, hipStream_t st) {
+  rt_status s;
+  const size_t pixmap_bytes = c->pixmap.bytes;
+  if ((s = ensure(c, c->pixmap, 4ull * npix)) != RT_OK) return s;
+  if (c->pixmap.bytes != pixmap_bytes) c->tiles_dev.clear();  // reallocated: the old map is gone
+  const bool same_tiles = c->pixmap_for == c->pixmap.ptr && c->pixmap_npix == npix && c->tiles_dev.size() == tl.size() &&
+                          std::memcmp(c->tiles_dev.data(), tl.data(), sizeof(uint4) * tl.size()) == 0;
+  if (!same_tiles) {  // the pixel map of an unchanged tile list is still in pixmap
+    if ((s = ensure(c, c->tiles, sizeof(uint4) * tl.size())) != RT_OK) return s;
+    c->tiles_dev = tl;  // the copy's source outlives this call
+    c->pixmap_for = c->pixmap.ptr;
+    c->pixmap_npix = npix;
+    RT_HIP(c, hipMemcpyAsync(c->tiles.ptr, c->tiles_dev.data(), sizeof(uint4) * tl.size(), hipMemcpyHostToDevice, st));
+    launch_pixmap((const uint4*)c->tiles.ptr, (uint32_t)tl.size(), npix, (uint32_t*)c->pixmap.ptr, st);
+  }
+  return RT_OK;
+}
+
+// The camera's view (make_view) in c->camx, copied on `st` when it differs from the one there.
+rt_status camera_view(rt_context* c, const rt_camera_desc* cam, hipStream_t st) {
+  rt_status s;
+  c->cam_host = make_view(cam);
+  if ((s = ensure(c, c->camx, sizeof(CamDev))) != RT_OK) return s;
+  if (!c->cam_valid || std::memcmp(&c->cam_dev, &c->cam_host, sizeof(CamDev)) != 0) {
+    RT_HIP(c, hipMemcpyAsync(c->camx.ptr, &c->cam_host, sizeof(CamDev), hipMemcpyHostToDevice, st));
+    c->cam_dev = c->cam_host;
+    c->cam_valid = true;
+  }
+  return RT_OK;
+}
+
 template <class R>
 rt_status render(rt_context* c, const rt_camera_desc* cam, const rt_render_params* prm, const rt_tile* tiles,
                  int32_t ntiles, void* out, int32_t out_dev, hipStream_t st) {
@@ -364,14 +411,8 @@ rt_status render(rt_context* c, const rt_camera_desc* cam, const rt_render_param
   }
 
   // pixel map: tiles packed in order, row-major inside each tile (expanded by k_pixmap)
-  std::vector<uint4> tl;
-  tl.reserve(ntiles);
   uint64_t npix64 = 0;
-  for (int t = 0; t < ntiles; t++) {
-    if (tiles[t].width == 0 || tiles[t].height == 0) continue;
-    tl.push_back(make_uint4((uint32_t)tiles[t].x0, (uint32_t)tiles[t].y0, (uint32_t)tiles[t].width, (uint32_t)npix64));
-    npix64 += (uint64_t)tiles[t].width * (uint64_t)tiles[t].height;
-  }
+  const std::vector<uint4> tl = pack_tiles(tiles, ntiles, npix64);
   if (npix64 >= (1ull << 31)) return set_err(c, RT_ERR_INVALID_ARGUMENT, "too many pixels in one call");
   const uint32_t npix = (uint32_t)npix64;
   if (npix == 0) return RT_OK;
@@ -416,21 +457,8 @@ rt_status render(rt_context* c, const rt_camera_desc* cam, const rt_render_param
     if ((s = ensure(c, c->partial, plan.partial_bytes)) != RT_OK) return s;
     c->last.passes += plan.passes;
     c->last.partial_bytes = plan.partial_bytes;
-    const size_t pixmap_bytes = c->pixmap.bytes;
-    if ((s = ensure(c, c->pixmap, 4ull * npix)) != RT_OK) return s;
-    if (c->pixmap.bytes != pixmap_bytes) c->tiles_dev.clear();  // reallocated: the old map is gone
     if ((s = ensure(c, c->blk, 4ull * (nblk_max + 2))) != RT_OK) return s;
-    const bool same_tiles = c->pixmap_for == c->pixmap.ptr && c->pixmap_npix == npix && c->tiles_dev.size() == tl.size() &&
-                            std::memcmp(c->tiles_dev.data(), tl.data(), sizeof(uint4) * tl.size()) == 0;
-    if (!same_tiles) {  // the pixel map of an unchanged tile list is still in pixmap
-      if ((s = ensure(c, c->tiles, sizeof(uint4) * tl.size())) != RT_OK) return s;
-      c->tiles_dev = tl;  // the copy's source outlives this call
-      c->pixmap_for = c->pixmap.ptr;
-      c->pixmap_npix = npix;
-      RT_HIP(c, hipMemcpyAsync(c->tiles.ptr, c->tiles_dev.data(), sizeof(uint4) * tl.size(), hipMemcpyHostToDevice,
-                               st));
-      launch_pixmap((const uint4*)c->tiles.ptr, (uint32_t)tl.size(), npix, (uint32_t*)c->pixmap.ptr, st);
-    }
+    if ((s = pixel_map(c, tl, npix, st)) != RT_OK) return s;
 
     unsigned char* sp = (unsigned char*)c->state.ptr;
     LaunchParams<R> p{};
@@ -461,13 +489,7 @@ rt_status render(rt_context* c, const rt_camera_desc* cam, const rt_render_param
     p.W = (uint32_t)cam->image_width;
     p.max_depth = prm->max_depth;
     p.seed = prm->seed;
-    c->cam_host = make_view(cam);
-    if ((s = ensure(c, c->camx, sizeof(CamDev))) != RT_OK) return s;
-    if (!c->cam_valid || std::memcmp(&c->cam_dev, &c->cam_host, sizeof(CamDev)) != 0) {
-      RT_HIP(c, hipMemcpyAsync(c->camx.ptr, &c->cam_host, sizeof(CamDev), hipMemcpyHostToDevice, st));
-      c->cam_dev = c->cam_host;
-      c->cam_valid = true;
-    }
+    if ((s = camera_view(c, cam, st)) != RT_OK) return s;
     p.cam_mode = c->cam_host.mode;
     p.camx = (const CamDev*)c->camx.ptr;
     if (p.cam_mode == RT_CAM_PERSPECTIVE) p.sc.cam64 = p.camx;
@@ -506,6 +528,31 @@ rt_status render(rt_context* c, const rt_camera_desc* cam, const rt_render_param
   return RT_OK;
 }
 
+// What a query or feature-buffer launch on `st` reads of the scene, in place: work of this context pending on another
+// stream is waited for (it reads the buffers written here and by the caller), then the scene blob of the precision
+// and the (object, material) tables are copied if rt_scene_upload has replaced them since, stream-ordered before
+// the kernel (a buffer of their own for the tables: the blobs stay the render kernels').
+rt_status query_scene(rt_context* c, bool f64, hipStream_t st) {
+  const CompiledScene& cs = c->scene;
+  bool& dirty = f64 ? c->scene_dirty64 : c->scene_dirty32;
+  if (c->pending && c->pend_stream != st) RT_HIP(c, hipStreamSynchronize(c->pend_stream));
+  if (dirty) {
+    const std::vector<unsigned char>& blob = f64 ? cs.blob64 : cs.blob32;
+    RT_HIP(c, hipMemcpyAsync(f64 ? c->scene64.ptr : c->scene32.ptr, blob.data(), blob.size(), hipMemcpyHostToDevice, st));
+    dirty = false;
+    c->pending = true;
+    c->pend_stream = st;
+  }
+  if (c->ids_dirty) {
+    if (!cs.ids.empty())
+      RT_HIP(c, hipMemcpyAsync(c->ids.ptr, cs.ids.data(), cs.ids.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    c->ids_dirty = false;
+    c->pending = true;
+    c->pend_stream = st;
+  }
+  return RT_OK;
+}
+
 // rt_trace_rays for one precision: n rays (0 < n < 2^31) through the family trace_family gives the scene.
 template <class R>
 rt_status trace_rays(rt_context* c, const rt_trace_params* prm, const double* rays, uint32_t n, double* geom,
@@ -514,29 +561,13 @@ rt_status trace_rays(rt_context* c, const rt_trace_params* prm, const double* ra
   const CompiledScene& cs = c->scene;
   const SceneHeader& hdr = f64 ? cs.hdr64 : cs.hdr;
   void* sbase = f64 ? c->scene64.ptr : c->scene32.ptr;
-  bool& dirty = f64 ? c->scene_dirty64 : c->scene_dirty32;
   const bool ordered = prm->traversal == RT_TRAV_ORDERED;
   const TraceFamily fam = trace_family(hdr, ordered, sizeof(typename WWord<R>::T));
   if (!family_built(trace_render_family(fam)))
     return set_err(c, RT_ERR_UNSUPPORTED,
                    std::string("this build (RT_DEV_ONLY) has no ") + trace_family_name(fam) + " query kernel");
-  // as render: work of this context pending on another stream reads the buffers written below
-  if (c->pending && c->pend_stream != st) RT_HIP(c, hipStreamSynchronize(c->pend_stream));
-  if (dirty) {  // the scene uploaded since the last launch of this precision, stream-ordered before the kernel
-    const std::vector<unsigned char>& blob = f64 ? cs.blob64 : cs.blob32;
-    RT_HIP(c, hipMemcpyAsync(sbase, blob.data(), blob.size(), hipMemcpyHostToDevice, st));
-    dirty = false;
-    c->pending = true;
-    c->pend_stream = st;
-  }
-  if (c->ids_dirty) {  // the same for the query tables (a buffer of their own: the blobs stay the render kernels')
-    if (!cs.ids.empty())
-      RT_HIP(c, hipMemcpyAsync(c->ids.ptr, cs.ids.data(), cs.ids.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    c->ids_dirty = false;
-    c->pending = true;
-    c->pend_stream = st;
-  }
   rt_status s;
+  if ((s = query_scene(c, f64, st)) != RT_OK) return s;
   TraceParams<R> p{};
   p.rays = rays;
   p.geom = geom;
@@ -569,6 +600,113 @@ rt_status trace_rays(rt_context* c, const rt_trace_params* prm, const double* ra
     RT_HIP(c, hipMemcpyAsync(ids, p.ids, 16ull * n, hipMemcpyDeviceToHost, st));
     RT_HIP(c, hipStreamSynchronize(st));
     if ((s = settle(c)) != RT_OK) return s;
+  }
+  return RT_OK;
+}
+
+// rt_camera_rays: the rays of samples [first_sample, first_sample + spp) of the tiles' pixels, n = npix * spp rows.
+rt_status camera_rays(rt_context* c, const rt_camera_desc* cam, uint64_t seed, int32_t first_sample, uint32_t spp,
+                      const std::vector<uint4>& tl, uint32_t npix, double* out, bool on_device, hipStream_t st) {
+  rt_status s;
+  // as render: work of this context pending on another stream reads the pixel map and the camera view
+  if (c->pending && c->pend_stream != st) RT_HIP(c, hipStreamSynchronize(c->pend_stream));
+  if ((s = pixel_map(c, tl, npix, st)) != RT_OK) return s;
+  if ((s = camera_view(c, cam, st)) != RT_OK) return s;
+  const uint64_t n = (uint64_t)npix * spp;
+  CamRayParams p{};
+  p.pixmap = (const uint32_t*)c->pixmap.ptr;
+  p.camx = (const CamDev*)c->camx.ptr;
+  p.rays = out;
+  if (!on_device) {
+    if ((s = ensure(c, c->q_rays, 64ull * n)) != RT_OK) return s;
+    p.rays = (double*)c->q_rays.ptr;
+  }
+  p.npix = npix;
+  p.spp = spp;
+  p.first_sample = (uint32_t)std::max(0, first_sample);
+  p.W = (uint32_t)cam->image_width;
+  p.cam_mode = c->cam_host.mode;
+  p.seed = seed;
+  launch_camera_rays(p, st);
+  RT_HIP(c, hipGetLastError());
+  c->pending = true;  // the launch reads the context's pixel map and camera view
+  c->pend_stream = st;
+  if (!on_device) {
+    RT_HIP(c, hipMemcpyAsync(out, p.rays, 64ull * n, hipMemcpyDeviceToHost, st));
+    RT_HIP(c, hipStreamSynchronize(st));
+    if ((s = settle(c)) != RT_OK) return s;
+  }
+  return RT_OK;
+}
+
+// rt_render_aov for one precision: npix pixels (0 < npix * spp < 2^31) through the family aov_family gives the scene.
+template <class R>
+rt_status render_aov(rt_context* c, const rt_camera_desc* cam, const rt_aov_params* prm, const std::vector<uint4>& tl,
+                     uint32_t npix, double* feat, int32_t* ids, hipStream_t st) {
+  const bool f64 = sizeof(R) == 8;
+  const CompiledScene& cs = c->scene;
+  const SceneHeader& hdr = f64 ? cs.hdr64 : cs.hdr;
+  const bool ordered = prm->traversal == RT_TRAV_ORDERED;
+  const TraceFamily fam = aov_family(hdr, ordered, sizeof(typename WWord<R>::T));
+  if (!family_built(trace_render_family(fam)))
+    return set_err(c, RT_ERR_UNSUPPORTED,
+                   std::string("this build (RT_DEV_ONLY) has no ") + trace_family_name(fam) + " feature-buffer kernel");
+  rt_status s;
+  if ((s = query_scene(c, f64, st)) != RT_OK) return s;
+  if ((s = pixel_map(c, tl, npix, st)) != RT_OK) return s;
+  if ((s = camera_view(c, cam, st)) != RT_OK) return s;
+  AovParams<R> p{};
+  p.feat = feat;
+  p.ids = ids;
+  if (!prm->on_device) {
+    if ((s = ensure(c, c->q_geom, 64ull * npix)) != RT_OK) return s;
+    if ((s = ensure(c, c->q_ids, 16ull * npix)) != RT_OK) return s;
+    p.feat = (double*)c->q_geom.ptr;
+    p.ids = (int32_t*)c->q_ids.ptr;
+  }
+  p.sc = dev_scene<R>(hdr, f64 ? c->scene64.ptr : c->scene32.ptr);
+  if (fam == TF_WIDE_HBM && (s = wide_spill_area<R>(c, hdr, p.sc)) != RT_OK) return s;
+  if (fam != TF_FLAT) p.sc.has_flat = 0;
+  if (ordered) p.sc.has_wide = 0;
+  p.sc.cam64 = nullptr;  // a near-edge quad hit is re-decided on the lane's own ray (quad_edge64), as in a query
+  p.pixmap = (const uint32_t*)c->pixmap.ptr;
+  p.camx = (const CamDev*)c->camx.ptr;
+  p.idtab = (const int2*)c->ids.ptr;
+  for (int k = 0; k < 4; k++) p.id_off[k] = cs.ids_off[k];
+  p.npix = npix;
+  p.spp = (uint32_t)prm->spp;
+  p.first_sample = (uint32_t)std::max(0, prm->first_sample);
+  p.W = (uint32_t)cam->image_width;
+  p.cam_mode = c->cam_host.mode;
+  p.ext = aov_extended(hdr, p.cam_mode) ? 1 : 0;
+  p.seed = prm->seed;
+  p.seg_shards = (unsigned long long*)c->counters.ptr;
+  launch_aov<R>(p, fam, st);
+  RT_HIP(c, hipGetLastError());
+  c->last.launches++;
+  c->pending = true;  // the segment counter (on the device) settles with rt_stats, as after a device-output render
+  c->pend_stream = st;
+  if (!prm->on_device) {
+    RT_HIP(c, hipMemcpyAsync(feat, p.feat, 64ull * npix, hipMemcpyDeviceToHost, st));
+    RT_HIP(c, hipMemcpyAsync(ids, p.ids, 16ull * npix, hipMemcpyDeviceToHost, st));
+    RT_HIP(c, hipStreamSynchronize(st));
+    if ((s = settle(c)) != RT_OK) return s;
+  }
+  return RT_OK;
+}
+
+// What rt_camera_rays and rt_render_aov check of a camera and a tile list (the checks of rt_render_tiles)
+rt_status check_camera_tiles(rt_context* c, const rt_camera_desc* cam, const rt_tile* tiles, int32_t ntiles) {
+  if (cam->mode < RT_CAM_PERSPECTIVE || cam->mode > RT_CAM_LENS)
+    return set_err(c, RT_ERR_INVALID_ARGUMENT, "unknown camera mode");
+  if (cam->image_width <= 0 || cam->image_height <= 0) return set_err(c, RT_ERR_INVALID_ARGUMENT, "empty image");
+  if (cam->image_width > 65535 || cam->image_height > 65535)  // pixel positions are packed x | y << 16
+    return set_err(c, RT_ERR_INVALID_ARGUMENT, "image wider or taller than 65535 pixels");
+  for (int t = 0; t < ntiles; t++) {
+    const rt_tile& tl = tiles[t];
+    if (tl.x0 < 0 || tl.y0 < 0 || tl.width < 0 || tl.height < 0 || tl.x0 + tl.width > cam->image_width ||
+        tl.y0 + tl.height > cam->image_height)
+      return set_err(c, RT_ERR_INVALID_ARGUMENT, "tile " + std::to_string(t) + " outside the image");
   }
   return RT_OK;
 }
@@ -768,6 +906,59 @@ rt_status rt_trace_rays(rt_context* c, const rt_trace_params* prm, const double*
   try {
     if (prm->precision == RT_PREC_F64) return trace_rays<double>(c, prm, rays, (uint32_t)nrays, out_geom, out_ids, st);
     return trace_rays<float>(c, prm, rays, (uint32_t)nrays, out_geom, out_ids, st);
+  } catch (const std::bad_alloc&) {
+    return set_err(c, RT_ERR_OUT_OF_MEMORY, "out of host memory");
+  }
+}
+
+rt_status rt_camera_rays(rt_context* c, const rt_camera_desc* cam, uint64_t seed, int32_t first_sample, int32_t spp,
+                         const rt_tile* tiles, int32_t ntiles, double* out_rays, int32_t on_device, void* stream) {
+  if (!c) return set_err(nullptr, RT_ERR_INVALID_ARGUMENT, "null context");
+  if (!cam || !tiles || !out_rays || ntiles < 0) return set_err(c, RT_ERR_INVALID_ARGUMENT, "null argument");
+  if (spp < 1) return set_err(c, RT_ERR_INVALID_ARGUMENT, "spp must be positive");
+  if (on_device && (uintptr_t)out_rays % 16 != 0)  // the kernel writes a ray as 16-byte words
+    return set_err(c, RT_ERR_INVALID_ARGUMENT, "device out_rays must be 16-byte aligned");
+  rt_status s;
+  if ((s = check_camera_tiles(c, cam, tiles, ntiles)) != RT_OK) return s;
+  try {
+    uint64_t npix = 0;
+    const std::vector<uint4> tl = pack_tiles(tiles, ntiles, npix);
+    if (npix * (uint64_t)spp >= (1ull << 31)) return set_err(c, RT_ERR_INVALID_ARGUMENT, "npix * spp outside [0, 2^31)");
+    if (npix == 0) return RT_OK;
+    RT_HIP(c, hipSetDevice(c->device));
+    // the stream as rt_trace_rays takes it: NULL is the null stream for device pointers, the context's own otherwise
+    hipStream_t st = (stream == nullptr && !on_device) ? c->stream : (hipStream_t)stream;
+    return camera_rays(c, cam, seed, first_sample, (uint32_t)spp, tl, (uint32_t)npix, out_rays, on_device != 0, st);
+  } catch (const std::bad_alloc&) {
+    return set_err(c, RT_ERR_OUT_OF_MEMORY, "out of host memory");
+  }
+}
+
+rt_status rt_render_aov(rt_context* c, const rt_camera_desc* cam, const rt_aov_params* prm, const rt_tile* tiles,
+                        int32_t ntiles, double* out_feat, int32_t* out_ids, void* stream) {
+  if (!c) return set_err(nullptr, RT_ERR_INVALID_ARGUMENT, "null context");
+  if (!cam || !prm || !tiles || !out_feat || !out_ids || ntiles < 0)
+    return set_err(c, RT_ERR_INVALID_ARGUMENT, "null argument");
+  if (prm->spp < 1) return set_err(c, RT_ERR_INVALID_ARGUMENT, "spp must be positive");
+  if (prm->precision != RT_PREC_F32 && prm->precision != RT_PREC_F64)
+    return set_err(c, RT_ERR_INVALID_ARGUMENT, "unknown precision");
+  if (prm->traversal != RT_TRAV_AUTO && prm->traversal != RT_TRAV_ORDERED)
+    return set_err(c, RT_ERR_INVALID_ARGUMENT, "unknown traversal");
+  if (prm->on_device && ((uintptr_t)out_feat | (uintptr_t)out_ids) % 16 != 0)  // both are written as 16-byte words
+    return set_err(c, RT_ERR_INVALID_ARGUMENT, "device out_feat and out_ids must be 16-byte aligned");
+  rt_status s;
+  if ((s = check_camera_tiles(c, cam, tiles, ntiles)) != RT_OK) return s;
+  if (!c->has_scene) return set_err(c, RT_ERR_NO_SCENE, "rt_scene_upload has not succeeded on this context");
+  try {
+    uint64_t npix = 0;
+    const std::vector<uint4> tl = pack_tiles(tiles, ntiles, npix);
+    if (npix * (uint64_t)prm->spp >= (1ull << 31))
+      return set_err(c, RT_ERR_INVALID_ARGUMENT, "npix * spp outside [0, 2^31)");
+    if (npix == 0) return RT_OK;
+    RT_HIP(c, hipSetDevice(c->device));
+    hipStream_t st = (stream == nullptr && !prm->on_device) ? c->stream : (hipStream_t)stream;
+    if (prm->precision == RT_PREC_F64) return render_aov<double>(c, cam, prm, tl, (uint32_t)npix, out_feat, out_ids, st);
+    return render_aov<float>(c, cam, prm, tl, (uint32_t)npix, out_feat, out_ids, st);
   } catch (const std::bad_alloc&) {
     return set_err(c, RT_ERR_OUT_OF_MEMORY, "out of host memory");
   }

@@ -90,6 +90,11 @@ class rt_trace_params(ctypes.Structure):
                 ("pad_", c_int32)]
 
 
+class rt_aov_params(ctypes.Structure):
+    _fields_ = [("seed", c_uint64), ("spp", c_int32), ("first_sample", c_int32), ("precision", c_int32),
+                ("traversal", c_int32), ("on_device", c_int32), ("pad_", c_int32)]
+
+
 # rt_trace_family_kind
 RT_TRACE_FLAT, RT_TRACE_LINEAR, RT_TRACE_WIDE_LDS, RT_TRACE_WIDE_HBM, RT_TRACE_STACK = range(5)
 TRACE_FAMILY_NAMES = ("FLAT", "LINEAR", "WIDE_LDS", "WIDE_HBM", "STACK")
@@ -114,6 +119,10 @@ SIGNATURES = {
     "rt_trace_rays": (c_int32, [ctypes.c_void_p, ctypes.POINTER(rt_trace_params), ctypes.c_void_p, ctypes.c_int64,
                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "rt_trace_family": (c_int32, [ctypes.c_void_p, c_int32, c_int32]),
+    "rt_camera_rays": (c_int32, [ctypes.c_void_p, ctypes.POINTER(rt_camera_desc), c_uint64, c_int32, c_int32,
+                                 ctypes.POINTER(rt_tile), c_int32, ctypes.c_void_p, c_int32, ctypes.c_void_p]),
+    "rt_render_aov": (c_int32, [ctypes.c_void_p, ctypes.POINTER(rt_camera_desc), ctypes.POINTER(rt_aov_params),
+                                ctypes.POINTER(rt_tile), c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "rt_multi_create": (c_int32, [ctypes.POINTER(c_int32), c_int32, ctypes.POINTER(ctypes.c_void_p)]),
     "rt_multi_destroy": (None, [ctypes.c_void_p]),
     "rt_multi_last_error": (ctypes.c_char_p, [ctypes.c_void_p]),

@@ -3,8 +3,11 @@
 write_ppm reproduces the reference's P3 writer: header "P3\\nW H\\n255\\n" (camera.h:149-151), then
 one "r g b" line per pixel with gamma 2.2 and int(255.999 * x) and no clamp (color.h:16-36), so
 values above 1 give numbers above 255 exactly as the reference prints them. write_pfm / read_pfm
-store the linear float framebuffer losslessly (Portable Float Map, little-endian, bottom row first).
+store the linear float framebuffer losslessly (Portable Float Map, little-endian, bottom row first);
+write_aov_pfm puts the feature buffers of Context.render_aov next to the beauty image in the same format.
 """
+import os
+
 import numpy as np
 
 
@@ -27,10 +30,12 @@ def write_ppm(image, path):
 
 
 def write_pfm(image, path):
+    """(H, W, 3) as a colour map ("PF"), (H, W) or (H, W, 1) as a greyscale one ("Pf")."""
     img = np.asarray(image, dtype=np.float32)
     h, w = img.shape[:2]
+    grey = img.ndim == 2 or img.shape[2] == 1
     with open(path, "wb") as f:
-        f.write(f"PF\n{w} {h}\n-1.0\n".encode())
+        f.write(f"{'Pf' if grey else 'PF'}\n{w} {h}\n-1.0\n".encode())
         f.write(np.ascontiguousarray(img[::-1].astype("<f4")).tobytes())
 
 
@@ -44,3 +49,18 @@ def read_pfm(path):
         ch = 3 if kind == b"PF" else 1
         data = np.frombuffer(f.read(), dtype="<f4" if scale < 0 else ">f4", count=w * h * ch)
     return data.reshape(h, w, ch)[::-1].astype(np.float32)
+
+
+def write_aov_pfm(aov, beauty_path):
+    """The channels of Context.render_aov (whole image) beside the beauty image `beauty_path`: <stem>.albedo.pfm and
+    <stem>.normal.pfm (colour), <stem>.depth.pfm and <stem>.hit.pfm (greyscale). Returns {channel: path}."""
+    stem = os.path.splitext(beauty_path)[0]
+    paths = {}
+    for name in ("albedo", "normal", "depth", "hit"):
+        ch = aov[name]
+        ch = ch.cpu().numpy() if hasattr(ch, "cpu") else np.asarray(ch)
+        if ch.ndim != (3 if name in ("albedo", "normal") else 2):
+            raise ValueError("write_aov_pfm takes whole-image channels (H, W[, 3]), not packed tiles")
+        paths[name] = f"{stem}.{name}.pfm"
+        write_pfm(ch, paths[name])
+    return paths

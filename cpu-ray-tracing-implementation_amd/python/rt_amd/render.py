@@ -14,6 +14,7 @@ class Context:
         if st != abi.RT_OK:
             raise abi.RTError(st, self.lib.rt_last_error(None).decode())
         self.h = h
+        self.device = device
 
     def close(self):
         if self.h:
@@ -115,6 +116,64 @@ class Context:
                                            ctypes.c_void_p(geom.data_ptr()), ctypes.c_void_p(ids.data_ptr()),
                                            ctypes.c_void_p(self._stream_handle(stream))))
         return geom, ids
+
+    def _tiles(self, cam, tiles):
+        """(ctypes tile array, count, pixels, whether it is the whole image as one tile)."""
+        full = tiles is None
+        if full:
+            tiles = [(0, 0, cam.image_width, cam.image_height)]
+        tl = tiles if isinstance(tiles, abi.TileList) else abi.TileList(tiles)
+        return tl.arr, len(tl), sum(t[2] * t[3] for t in tl), full
+
+    def camera_rays(self, cam, spp, seed=1, first_sample=0, tiles=None, device=False, stream=None):
+        """The camera rays a render draws, (npix * spp, 8) float64 rows o[3], d[3], time, tmax = inf in trace_rays'
+        format: row pix * spp + s is sample first_sample + s of pixel pix, pixels packed as render packs its tiles
+        (default: the whole image, row-major). Needs no scene. device=False: a numpy array; device=True: a torch
+        tensor on the context's device, the call ordered on `stream` (default torch's current stream)."""
+        arr, nt, npix, _ = self._tiles(cam, tiles)
+        n = npix * spp
+        if not device:
+            out = np.empty((max(n, 1), 8), dtype=np.float64)[:n]
+            self._check(self.lib.rt_camera_rays(self.h, ctypes.byref(cam), seed, first_sample, spp, arr, nt,
+                                                ctypes.c_void_p(out.ctypes.data), 0, ctypes.c_void_p(0)))
+            return out
+        import torch
+        dev = torch.device("cuda", self.device)
+        out = torch.empty((max(n, 1), 8), dtype=torch.float64, device=dev)[:n]
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        self._check(self.lib.rt_camera_rays(self.h, ctypes.byref(cam), seed, first_sample, spp, arr, nt,
+                                            ctypes.c_void_p(out.data_ptr()), 1,
+                                            ctypes.c_void_p(self._stream_handle(stream))))
+        return out
+
+    def render_aov(self, cam, spp, seed=1, precision=abi.RT_PREC_F32, traversal=0, first_sample=0, tiles=None,
+                   device=False, stream=None):
+        """The first-hit feature buffers of the frame, the means over samples [first_sample, first_sample + spp) of
+        each pixel: dict(albedo (.., 3), normal (.., 3), depth (..), hit (..), ids (.., 4) int32 object, material,
+        kind, front of sample first_sample). Shapes are (H, W, ..) for the whole image, (npix, ..) for given tiles.
+        float64 for both precisions. device=False: numpy arrays, filled on return; device=True: torch tensors (views
+        of one buffer) on the context's device, the call ordered on `stream` (default torch's current stream)."""
+        arr, nt, npix, full = self._tiles(cam, tiles)
+        prm = abi.rt_aov_params(seed=seed, spp=spp, first_sample=first_sample, precision=precision,
+                                traversal=traversal, on_device=1 if device else 0)
+        if not device:
+            feat = np.zeros((max(npix, 1), 8), dtype=np.float64)[:npix]
+            ids = np.full((max(npix, 1), 4), -1, dtype=np.int32)[:npix]
+            fp, ip, sp = feat.ctypes.data, ids.ctypes.data, 0
+        else:
+            import torch
+            dev = torch.device("cuda", self.device)
+            feat = torch.zeros((max(npix, 1), 8), dtype=torch.float64, device=dev)[:npix]
+            ids = torch.full((max(npix, 1), 4), -1, dtype=torch.int32, device=dev)[:npix]
+            if stream is None:
+                stream = torch.cuda.current_stream(dev)
+            fp, ip, sp = feat.data_ptr(), ids.data_ptr(), self._stream_handle(stream)
+        self._check(self.lib.rt_render_aov(self.h, ctypes.byref(cam), ctypes.byref(prm), arr, nt, ctypes.c_void_p(fp),
+                                           ctypes.c_void_p(ip), ctypes.c_void_p(sp)))
+        shape = (cam.image_height, cam.image_width) if full else (npix,)
+        return dict(albedo=feat[:, 0:3].reshape(*shape, 3), normal=feat[:, 3:6].reshape(*shape, 3),
+                    depth=feat[:, 6].reshape(*shape), hit=feat[:, 7].reshape(*shape), ids=ids.reshape(*shape, 4))
 
     @staticmethod
     def _stream_handle(stream):

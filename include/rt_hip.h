@@ -335,6 +335,55 @@ rt_status rt_trace_rays(rt_context* ctx, const rt_trace_params* params, const do
  * for an unknown precision or traversal. */
 int32_t rt_trace_family(rt_context* ctx, int32_t precision, int32_t traversal);
 
+/* ---- camera rays and feature buffers (AOVs): what a frame's pixels see first ----
+ *
+ * rt_camera_rays writes the rays camera::generate_ray (camera.h:244-293) draws for a render, in rt_trace_rays'
+ * format: out_rays holds npix * spp rows of 8 doubles, o[3], d[3], time, tmax = +inf. Pixels are those of the tiles,
+ * packed as rt_render_tiles packs them; row pix * spp + s is sample first_sample + s of pixel pix, keyed
+ * (seed, y * W + x, first_sample + s) like the render's: the same draws (the lens disk's rejection draws and the
+ * time draw included), built in fp64 as the render builds them for both precisions. A negative first_sample counts
+ * as 0, as in rt_render_params. Needs no scene. on_device / stream: as rt_trace_params.on_device.
+ * RT_ERR_INVALID_ARGUMENT: a null pointer, spp < 1, an unknown camera mode, an empty image or one wider or taller
+ * than 65535, a tile outside the image, npix * spp >= 2^31, a device out_rays not aligned to 16 bytes. No tile with
+ * pixels launches nothing. Does not touch rt_counters. */
+rt_status rt_camera_rays(rt_context* ctx, const rt_camera_desc* cam, uint64_t seed, int32_t first_sample, int32_t spp,
+                         const rt_tile* tiles, int32_t ntiles, double* out_rays, int32_t on_device, void* stream);
+
+/* rt_render_aov: per pixel the albedo, shading normal, depth and hit share, the guide channels of a denoiser or a
+ * compositor, over the same camera samples as the beauty image. No reference counterpart as an entry point: it is
+ * the first segment of camera::ray_color (camera.h:193-200) with the hit record and the texture written out.
+ *
+ * out_feat: npix x 8 doubles, albedo[3], normal[3], depth, hit; tiles packed as in rt_render_tiles. Every channel
+ * is (1 / spp) x the sum over samples [first_sample, first_sample + spp) of the pixel, added in increasing sample
+ * order in double for both precisions: a pixel's value does not depend on the tiling, the tile order or the GPU.
+ * A sample's ray is rt_camera_rays' and goes through world.hit(r, interval(0.001, inf)) as in rt_trace_rays. It adds
+ *   albedo  on a hit the hit material's texture (rt_material.texture; a volume's phase material's) sampled at the
+ *           hit's (u, v, p) -- the value ray_color uses as attenuation or emission; u, v a quad's alpha, beta
+ *           (quad.h:58-62), a sphere's get_sphere_uv (sphere.h:70), 0 for triangles and volumes. On a miss what
+ *           camera::miss returns (camera.h:180-190): the background texture through its unit-sphere test, or 0;
+ *   normal  on a hit rt_trace_rays' n (face-forwarded, world space; a moving sphere's is not a unit vector, a
+ *           volume's is (1, 0, 0)), 0 on a miss;
+ *   depth   on a hit t |d|, the distance from the ray's origin, 0 on a miss;
+ *   hit     1 on a hit, 0 on a miss (divide the other sums by it for means over the hits).
+ * out_ids: npix x 4 int32, object, material, kind, front of sample first_sample as rt_trace_rays reports them
+ * (a miss: all -1).
+ * volumne::hit draws as bounce 0 of the pixel's own path (seed, y * W + x, sample). With spp = 1, first_sample = 0
+ * and one tile that is the whole image, ray index equals pixel index and the pass equals rt_trace_rays on
+ * rt_camera_rays' output, volume scenes included. */
+typedef struct rt_aov_params {
+  uint64_t seed;
+  int32_t spp, first_sample; /* camera samples [first_sample, first_sample + spp) of each pixel, spp >= 1 */
+  int32_t precision;         /* rt_precision: the traversal's arithmetic; the outputs are doubles either way */
+  int32_t traversal;         /* rt_traversal */
+  int32_t on_device, pad_;   /* 1: out_feat and out_ids are device pointers, the call is stream-ordered */
+} rt_aov_params;
+/* The errors of rt_camera_rays and rt_trace_rays (device out_feat and out_ids aligned to 16 bytes), and
+ * RT_ERR_NO_SCENE. The traversal is rt_trace_family's, except that a scene with an RT_TEX_IMAGE texture leaves the
+ * flat program for the linear one (the flat program's hit carries no u, v). Adds npix * spp to rt_counters.segments
+ * and 1 to launches; with on_device = 1 the call joins the context's outstanding work as a device-output render. */
+rt_status rt_render_aov(rt_context* ctx, const rt_camera_desc* cam, const rt_aov_params* params, const rt_tile* tiles,
+                        int32_t ntiles, double* out_feat, int32_t* out_ids, void* stream);
+
 /* ---- multi-GPU driver: the framebuffer tiled over the devices of one node ----
  *
  * Replaces camera::render's per-row std::for_each(par_unseq) (camera.h:154-172) when a
