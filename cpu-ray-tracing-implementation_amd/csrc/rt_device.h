@@ -9,6 +9,7 @@
 
 #include <type_traits>
 
+#include "rt_room.h"
 #include "rt_scene.h"
 #include "rt_sin.h"
 #include "rt_types.h"
@@ -1590,8 +1591,8 @@ __device__ __forceinline__ void trace_linear(const DevScene<R>& sc, V<R> wo, V<R
 }
 
 // ------------------------------------------------------------------ flat program
-// rt_scene.h FlatQuadT / FlatBoxT: world-space axis-aligned quads in three branch-free loops
-// (one per plane axis, records scalar-loaded in pairs), then the slab tests of the boxes.
+// rt_scene.h FlatQuadT / FlatRoomT / FlatBoxT: world-space axis-aligned quads in three branch-free loops
+// (one per plane axis, records scalar-loaded in pairs), then the slab tests of the rooms and of the boxes.
 // A quad is the aquad_t test (quad.h:30-64 for n = +-e_A); the record index of the closest
 // hit is kept and turned into (entry, instance) once at the end. fp64 (round 3): the same
 // program with the per-ray reciprocal 1/d in IEEE double, so a quad costs multiplies instead
@@ -1678,11 +1679,32 @@ __device__ __forceinline__ Slab<R> flat_slab(const FlatBoxT<R>& b, V<R> o, V<R> 
   s.th = s.tn >= tmin ? s.tn : s.tf;
   return s;
 }
-// fq / fb: where the hit's record is read at the end (the scene's, or the kernel's LDS copy)
+// A room (rt_scene.h FlatRoomT): the walls' quad tests as one slab test with rt_room.h's rule, the six distances
+// computed as flat_slab computes them (each is its wall's quad-test distance bit for bit). fp32 excludes the
+// wall the ray leaves as the boxes do, the distance to its plane becoming -inf; the wall is the face whose
+// entry is excl_e (a room's faces have no quad copies to number them). fp64 excludes nothing (flat_slab's note).
+template <class R>
+__device__ __forceinline__ RoomHit<R> flat_room_test(const FlatRoomHeadT<R>& b, V<R> o, V<R> inv, R tmin,
+                                                     uint32_t excl_e, int32_t excl_i) {
+  auto dist = [&](R p, R oa, R ia) { return (p - oa) * ia; };
+  R t0[3] = {dist(b.lo[0], o.x, inv.x), dist(b.lo[1], o.y, inv.y), dist(b.lo[2], o.z, inv.z)};
+  R t1[3] = {dist(b.hi[0], o.x, inv.x), dist(b.hi[1], o.y, inv.y), dist(b.hi[2], o.z, inv.z)};
+  if constexpr (sizeof(R) == 4) {
+    const bool left = excl_i == b.inst;
+    const R ninf = -Num<R>::inf();
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+      t0[k] = (left & (excl_e == b.e[2 * k]) & ((b.present >> (2 * k)) & 1u)) ? ninf : t0[k];
+      t1[k] = (left & (excl_e == b.e[2 * k + 1]) & ((b.present >> (2 * k + 1)) & 1u)) ? ninf : t1[k];
+    }
+  }
+  return room_rule<R>(t0, t1, b.present, tmin);
+}
+// fq / fr / fb: where the hit's record is read at the end (the scene's, or the kernel's LDS copy)
 template <class R>
 __device__ __forceinline__ void trace_flat(const DevScene<R>& sc, V<R> o, V<R> d, uint32_t excl_e, int32_t excl_i,
                                            R& t_best, uint32_t& e_best, int32_t& i_best, uint32_t& nm,
-                                           const FlatQuadT<R>* fq, const FlatBoxT<R>* fb) {
+                                           const FlatQuadT<R>* fq, const FlatRoomT<R>* fr, const FlatBoxT<R>* fb) {
   const R tmin = R(0.001);
   R tmax = Num<R>::inf();
   const V<R> inv = flat_inv(d);
@@ -1693,6 +1715,17 @@ __device__ __forceinline__ void trace_flat(const DevScene<R>& sc, V<R> o, V<R> d
   flat_quads<0>(sc.flatq, n0, 0, o, d, inv, tmin, tmax, best, xkey);
   flat_quads<1>(sc.flatq + n0, n1, (int32_t)n0, o, d, inv, tmin, tmax, best, xkey);
   flat_quads<2>(sc.flatq + n0 + n1, n2, (int32_t)(n0 + n1), o, d, inv, tmin, tmax, best, xkey);
+  // rooms: best = nq + 8 room + face (none in the fp32 blob: rt_scene.h kFlatRoomsF32)
+  const uint32_t nr8 = (sizeof(R) == 8 || kFlatRoomsF32) ? 8u * sc.n_flatr : 0u;
+  const FlatRoomT<R>* rooms = flat_rooms(sc);
+#pragma unroll 1
+  for (uint32_t k = 0; k < nr8; k += 8u) {
+    const FlatRoomHeadT<R> b = ld_scalar(reinterpret_cast<const FlatRoomHeadT<R>*>(rooms + (k >> 3)));
+    const RoomHit<R> r = flat_room_test(b, o, inv, tmin, excl_e, excl_i);
+    const bool h = r.hit & (r.t <= tmax);
+    tmax = h ? r.t : tmax;
+    best = h ? (int32_t)(nq + k) + r.face : best;
+  }
 #pragma unroll 1
   for (uint32_t k = 0; k < sc.n_flatb; k++) {
     const FlatBoxT<R> b = ld_scalar(sc.flatb + k);
@@ -1701,7 +1734,7 @@ __device__ __forceinline__ void trace_flat(const DevScene<R>& sc, V<R> o, V<R> d
     // tf >= max(tn, tmin) is the first two (round 6: C2 fp64 25.28 -> 25.27 ms/frame, fp32 18.37 -> 18.34, r06g)
     const bool h = (s.tf >= fmax(s.tn, tmin)) & (s.th <= tmax);
     tmax = h ? s.th : tmax;
-    best = h ? (int32_t)(nq + k) : best;
+    best = h ? (int32_t)(nq + nr8 + k) : best;
   }
   t_best = tmax;
   e_best = kNoHit;
@@ -1715,9 +1748,17 @@ __device__ __forceinline__ void trace_flat(const DevScene<R>& sc, V<R> o, V<R> d
     nm = r.nm;
     return;
   }
+  if ((uint32_t)best < nq + nr8) {  // a room's wall: its own entry and nm from the record
+    const uint32_t j = (uint32_t)best - nq;
+    const FlatRoomT<R>& r = fr[j >> 3];
+    e_best = r.e[j & 7u];
+    i_best = r.inst;
+    nm = r.nm[j & 7u];
+    return;
+  }
   // the face of the box: the axis whose slab bound is the hit distance (recomputed exactly
   // as in the loop), on the side the ray enters (or leaves, from inside)
-  const FlatBoxT<R>& b = fb[(uint32_t)best - nq];
+  const FlatBoxT<R>& b = fb[(uint32_t)best - nq - nr8];
   const Slab<R> s = flat_slab(b, o, inv, tmin, excl_i, xf);
   const bool enter = s.tn >= tmin;
   int k = 2;

@@ -939,26 +939,32 @@ struct FlatTrav : TravDefaults {
   template <class PS>
   __device__ __forceinline__ static void run(const DevScene<R>& sc, const Node<R>*, const PS& s, Keys, uint32_t*,
                                              R& t, uint32_t& e, int32_t& i, uint32_t& nm) {
-    trace_flat<R>(sc, s.o, s.d, s.xe, s.xi, t, e, i, nm, sc.flatq, sc.flatb);
+    trace_flat<R>(sc, s.o, s.d, s.xe, s.xi, t, e, i, nm, sc.flatq, flat_rooms(sc), sc.flatb);
   }
   // the scene's small tables copied into LDS (persistent kernel): the hit's record and
   // material are then LDS reads instead of dependent global loads
   // (the LL kernel's tables are smaller, so a 256-lane block's LDS -- tables plus the fp64 cold path state,
   // ~27 KB with the general sizes -- leaves room for 6 blocks per CU)
-  static constexpr uint32_t kLdsQuads = LL ? 16 : 64, kLdsBoxes = LL ? 8 : 16, kLdsMats = LL ? 16 : 32;
+  // (the fp64 LL kernel's 7 blocks per CU leave no whole 512-byte LDS granule: its one room record, 112 B, takes
+  // the place of two of its 16 quad slots, 128 B -- a room stands for five or six quads)
+  static constexpr uint32_t kLdsQuads = LL ? 14 : 64, kLdsBoxes = LL ? 8 : 16, kLdsMats = LL ? 16 : 32;
+  static constexpr uint32_t kLdsRooms = LL ? 1 : 2;
   struct Tables {
     FlatQuadT<R> q[kLdsQuads];
+    FlatRoomT<R> r[kLdsRooms];
     FlatBoxT<R> b[kLdsBoxes];
     Material<R> m[LL ? 1 : kLdsMats];
     R4<R> lm[LL ? kLdsMats : 1];  // LL: (solid colour, 1 for diffuse_light)
   };
   __host__ __device__ __forceinline__ static bool tables_fit(const DevScene<R>& sc) {
     return sc.n_flatq[0] + sc.n_flatq[1] + sc.n_flatq[2] <= kLdsQuads && sc.n_flatb <= kLdsBoxes &&
-           sc.n_mats <= kLdsMats;
+           sc.n_flatr <= kLdsRooms && sc.n_mats <= kLdsMats;
   }
   __device__ __forceinline__ static void fill(const DevScene<R>& sc, Tables& tb) {
     const uint32_t nq = sc.n_flatq[0] + sc.n_flatq[1] + sc.n_flatq[2];
     for (uint32_t j = threadIdx.x; j < nq; j += kBlock) tb.q[j] = sc.flatq[j];
+    if constexpr (sizeof(R) == 8 || kFlatRoomsF32)
+      for (uint32_t j = threadIdx.x; j < sc.n_flatr; j += kBlock) tb.r[j] = flat_rooms(sc)[j];
     for (uint32_t j = threadIdx.x; j < sc.n_flatb; j += kBlock) tb.b[j] = sc.flatb[j];
     for (uint32_t j = threadIdx.x; j < sc.n_mats; j += kBlock) {
       if constexpr (LL) {
@@ -972,7 +978,7 @@ struct FlatTrav : TravDefaults {
   template <class PS>
   __device__ __forceinline__ static void run_lds(const DevScene<R>& sc, const Tables& tb, const PS& s, R& t,
                                                  uint32_t& e, int32_t& i, uint32_t& nm) {
-    trace_flat<R>(sc, s.o, s.d, s.xe, s.xi, t, e, i, nm, tb.q, tb.b);
+    trace_flat<R>(sc, s.o, s.d, s.xe, s.xi, t, e, i, nm, tb.q, tb.r, tb.b);
   }
 };
 // LDSN: the scene's BVH nodes (at most kLdsNodeMax) are copied into LDS at kernel start, so

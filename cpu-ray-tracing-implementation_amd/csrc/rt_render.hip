@@ -194,6 +194,7 @@ DevScene<R> dev_scene(const SceneHeader& h, void* base) {
   s.flatb = (const FlatBoxT<R>*)at(h.off_flat_box);
   for (int a = 0; a < 3; a++) s.n_flatq[a] = h.n_flat_quad[a];
   s.n_flatb = h.n_flat_box;
+  s.n_flatr = h.n_flat_room;  // the records follow the boxes (flat_rooms)
   s.n_mats = h.n_mats;
   s.root = h.root;
   s.background = h.background;

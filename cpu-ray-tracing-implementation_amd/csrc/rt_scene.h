@@ -78,7 +78,8 @@ static_assert(3 * kMaxChain <= 14, "an instance chain must fit one LinRec");
 // under translate-only instances, is rewritten in world space (translations folded into the
 // records) and regrouped by plane axis, so a wave runs three branch-free loops with no per-op
 // dispatch. An instance holding exactly the six quads of `box()` (quad.h:91-112) with one
-// lambertian material becomes one slab-test record. Both blobs carry it (FlatQuadT<float> /
+// lambertian material becomes one slab-test record (FlatBoxT); five or six quads that are the faces of
+// one box become one room record (FlatRoomT) and leave the quad groups. Both blobs carry it (FlatQuadT<float> /
 // <double>): the fp32 kernels use it by default; the fp64 kernels too (round 3), where it agrees
 // with the reference-ordered linear program up to rounding (t as (plane - o_A) * (1/d_A) instead
 // of a division per quad); RT_TRAV_ORDERED keeps the linear program. Order inside the scene only
@@ -111,7 +112,38 @@ struct alignas(16) FlatBoxT {
   uint32_t pad;
 };
 using FlatBox = FlatBoxT<float>;
+//   FlatRoomT: five or six world-level quads (or quads of one translate-only instance) that are the faces of
+//   one axis-aligned box [lo, hi] -- a Cornell box's walls, an open or closed room; any materials -- become
+//   one record tested with a single slab test (rt_room.h room_rule). present: bit 2k + s set when the face on
+//   plane lo_k (s = 0) / hi_k (s = 1) exists; e[f], nm[f]: that face's own quad entry and nm, as its FlatQuadT
+//   would hold them (the faces get no quad copies). Rooms are tested after the quad groups and before the
+//   boxes, so a floor and a box bottom at the same height tie as before. The tests read the record's head.
+template <class R>
+struct alignas(16) FlatRoomHeadT {
+  R lo[3];
+  R hi[3];
+  int32_t inst;  // translate-only instance of the faces, -1 at world level
+  uint32_t present;
+  uint32_t e[6];
+};
+template <class R>
+struct alignas(16) FlatRoomT {
+  R lo[3];
+  R hi[3];
+  int32_t inst;
+  uint32_t present;
+  uint32_t e[6];
+  uint32_t nm[6];
+};
+using FlatRoom = FlatRoomT<float>;
+// Rooms are in the fp64 blob only; the fp32 blob keeps a room's walls as quads (the two blobs are built
+// separately). An fp32 quad test is cheap -- fp32 arithmetic issues at twice the rate of the slab's min / max and
+// compares -- and the fp32 rule also has to find the wall a ray leaves among the record's entries: C2 fp32
+// measured 18.31 -> 19.55 ms/frame with rooms. true compiles the fp32 form in (trace_flat).
+constexpr bool kFlatRoomsF32 = false;
 static_assert(sizeof(FlatQuadT<float>) == 32 && sizeof(FlatQuadT<double>) == 64, "flat quad records");
+static_assert(sizeof(FlatRoomT<float>) == 80 && sizeof(FlatRoomT<double>) == 112, "flat room records");
+static_assert(sizeof(FlatRoomHeadT<float>) == 64 && sizeof(FlatRoomHeadT<double>) == 80, "flat room heads");
 static_assert(sizeof(FlatBoxT<float>) == 64 && sizeof(FlatBoxT<double>) == 96, "flat box records");
 
 // quad.h:9-23 precomputed: n = unit(cross(u,v)), D = dot(n, corner),
@@ -331,6 +363,9 @@ struct SceneHeader {
   int32_t light_kind;   // L_* of the importance-sampling light
   int32_t light_aligned;
   uint32_t wide_top;    // the wide tree's first levels, breadth-first: nodes [0, wide_top) (LDS copy, HBM trees)
+  // flat program: rooms (FlatRoomT), stored directly after the boxes: off_flat_room = off_flat_box + boxes' bytes
+  uint32_t n_flat_room;
+  uint64_t off_flat_room;
 };
 
 }  // namespace rtd

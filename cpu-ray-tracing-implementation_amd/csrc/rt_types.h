@@ -95,6 +95,7 @@ struct DevScene {
   const double* texdata;  // procedural-texture tables (Texture::data)
   const uint8_t* images;  // picture-texture pixels (Texture::data)
   int32_t has_procedural; // any perlin / value / worley / voronoi texture: the EXT kernels
+  uint32_t n_flatr;       // flat program: rooms, stored directly after the boxes (flat_rooms)
   // wide BVH (rt_scene.h WNode; float boxes in both blobs): nodes, primitive words, root code,
   // stack need, WK_* kinds
   const WNode* wnodes;
@@ -113,6 +114,12 @@ struct DevScene {
   uint32_t* wide_spill;
   uint32_t spill_lanes;
 };
+// The flat program's room records follow its boxes in the blob (no pointer of their own: the view keeps its size
+// and the offsets of every other field, so kernels that use no flat program compile to the same code).
+template <class R>
+__host__ __device__ __forceinline__ const FlatRoomT<R>* flat_rooms(const DevScene<R>& sc) {
+  return reinterpret_cast<const FlatRoomT<R>*>(sc.flatb + sc.n_flatb);
+}
 // Trees in HBM: the tree's first levels are read from an LDS copy (trace_wide), at most this many nodes
 // (the builder orders up to kWideTopMax breadth-first); fp64 rays read them in the fp16 form (WNodeH)
 #ifndef RT_WIDE_TOP_N

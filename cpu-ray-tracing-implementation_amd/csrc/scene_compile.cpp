@@ -195,7 +195,8 @@ class Compiler {
   int make_instance(const std::vector<Op>& chain, uint32_t blas);
   LinRec<double> lin_record(uint32_t op) const;
   bool flat_program(const std::vector<uint32_t>& lin, std::vector<FlatQuadT<double>>& quads, uint32_t nq[3],
-                    std::vector<FlatBoxT<double>>& boxes);
+                    std::vector<FlatBoxT<double>>& boxes, std::vector<FlatRoomT<double>>& rooms,
+                    std::vector<FlatQuadT<double>>& quads_all, uint32_t nq_all[3]);
   bool wide_bvh(const std::vector<Item>& prims, CompiledScene* out);
   bool box_of_quads(const std::vector<Item>& prims, double lo[3], double hi[3]) const;
   std::vector<int> aligned_;  // per quad: 1 + perm for axis-aligned quads, 0 otherwise
@@ -907,8 +908,11 @@ LinRec<double> Compiler::lin_record(uint32_t op) const {
 // The flat program of rt_scene.h: the linear program's ops are all axis-aligned quads, at world
 // level or in translate-only instances. Returns false (no flat program) for anything else. The
 // records come out in double (the fp64 blob) and are rounded once for the fp32 blob (flat32).
+// quads / nq: the quad groups without the faces of rooms; quads_all / nq_all: with them (a blob that keeps
+// its walls as quads), in the same order.
 bool Compiler::flat_program(const std::vector<uint32_t>& lin, std::vector<FlatQuadT<double>>& quads, uint32_t nq[3],
-                            std::vector<FlatBoxT<double>>& boxes) {
+                            std::vector<FlatBoxT<double>>& boxes, std::vector<FlatRoomT<double>>& rooms,
+                            std::vector<FlatQuadT<double>>& quads_all, uint32_t nq_all[3]) {
   struct Q {
     uint32_t e;
     int32_t inst;
@@ -931,8 +935,12 @@ bool Compiler::flat_program(const std::vector<uint32_t>& lin, std::vector<FlatQu
     }
     return true;
   };
-  std::vector<FlatQuadT<double>> grp[3];
-  auto add_quad = [&](const Q& q, const double* off) {
+  std::vector<FlatQuadT<double>> grp[3], grp_all[3];
+  auto nm_of = [&](const Q& q) {
+    const Quad<double>& qq = quads_[epay(q.e)];
+    return (uint32_t)qq.mat | (uint32_t)q.A << 28 | (qq.n[q.A] < 0 ? 1u << 31 : 0u);
+  };
+  auto add_quad = [&](const Q& q, const double* off, bool in_room) {
     FlatQuadT<double> r{};
     r.plane = q.plane + off[q.A];
     r.lo_u = q.lo_u + off[q.U];
@@ -941,9 +949,80 @@ bool Compiler::flat_program(const std::vector<uint32_t>& lin, std::vector<FlatQu
     r.inv_w = 1.0 / q.len_w;
     r.e = q.e;
     r.inst = q.inst;
-    const Quad<double>& qq = quads_[epay(q.e)];
-    r.nm = (uint32_t)qq.mat | (uint32_t)q.A << 28 | (qq.n[q.A] < 0 ? 1u << 31 : 0u);
-    grp[q.A].push_back(r);
+    r.nm = nm_of(q);
+    grp_all[q.A].push_back(r);
+    if (!in_room) grp[q.A].push_back(r);
+  };
+  // Quads that are not a box() record wait here in program order, each with the pool it may form a room in:
+  // the world level, or its translate-only instance.
+  struct Pending {
+    Q q;
+    double off[3];
+    int pool;
+    bool in_room;
+  };
+  std::vector<Pending> pend;
+  int pools = 1;  // pool 0: the world level
+  auto span = [](double a, double len, double& s0, double& s1) { s0 = std::min(a, a + len), s1 = std::max(a, a + len); };
+  // the extent of q on axis k (an in-plane axis of q)
+  auto extent = [&](const Q& q, int k, double& s0, double& s1) {
+    if (k == q.U) span(q.lo_u, q.len_u, s0, s1);
+    else span(q.lo_w, q.len_w, s0, s1);
+  };
+  // Five or six quads of one pool that are the faces of one axis-aligned box -> one room record (rt_scene.h
+  // FlatRoomT): two planes lo < hi per axis at most, every quad spanning the box exactly in its two in-plane
+  // axes, no face twice. Anything else -- four walls, a shorter or a shifted wall -- stays quads.
+  auto find_rooms = [&](int pool) {
+    std::vector<size_t> ix;
+    for (size_t k = 0; k < pend.size(); k++)
+      if (pend[k].pool == pool) ix.push_back(k);
+    for (size_t i : ix) {
+      if (pend[i].in_room) continue;
+      const Q& a = pend[i].q;
+      for (size_t j : ix) {
+        const Q& b = pend[j].q;
+        if (pend[i].in_room) break;
+        if (j == i || pend[j].in_room || b.A == a.A) continue;
+        // a fixes the box in its two in-plane axes, b (in a plane across a's) along a's plane axis
+        double lo[3], hi[3];
+        extent(a, a.U, lo[a.U], hi[a.U]);
+        extent(a, a.W, lo[a.W], hi[a.W]);
+        extent(b, a.A, lo[a.A], hi[a.A]);
+        if (!(lo[0] < hi[0] && lo[1] < hi[1] && lo[2] < hi[2])) continue;
+        size_t face[6];
+        uint32_t present = 0;
+        bool twice = false;
+        for (size_t k : ix) {
+          const Q& q = pend[k].q;
+          if (pend[k].in_room || (q.plane != lo[q.A] && q.plane != hi[q.A])) continue;
+          double u0, u1, w0, w1;
+          extent(q, q.U, u0, u1);
+          extent(q, q.W, w0, w1);
+          if (u0 != lo[q.U] || u1 != hi[q.U] || w0 != lo[q.W] || w1 != hi[q.W]) continue;
+          const int f = 2 * q.A + (q.plane == hi[q.A] ? 1 : 0);
+          twice = twice || ((present >> f) & 1u);
+          present |= 1u << f;
+          face[f] = k;
+        }
+        int n = 0;
+        for (int f = 0; f < 6; f++) n += (present >> f) & 1u;
+        if (twice || n < 5 || !((present >> (2 * a.A + (a.plane == hi[a.A] ? 1 : 0))) & 1u)) continue;
+        FlatRoomT<double> r{};
+        for (int k = 0; k < 3; k++) {
+          r.lo[k] = lo[k] + pend[i].off[k];
+          r.hi[k] = hi[k] + pend[i].off[k];
+        }
+        r.inst = a.inst;
+        r.present = present;
+        for (int f = 0; f < 6; f++) {
+          if (!((present >> f) & 1u)) continue;
+          r.e[f] = pend[face[f]].q.e;
+          r.nm[f] = nm_of(pend[face[f]].q);
+          pend[face[f]].in_room = true;
+        }
+        rooms.push_back(r);
+      }
+    }
   };
   // six quads of box() (quad.h:91-112) with one lambertian material -> one slab record
   auto as_box = [&](const std::vector<Q>& qs, const double* off, FlatBoxT<double>& b) {  // b.face: original entries
@@ -979,7 +1058,6 @@ bool Compiler::flat_program(const std::vector<uint32_t>& lin, std::vector<FlatQu
     b.mat = (uint32_t)mat;
     return true;
   };
-  const double zero[3] = {0, 0, 0};
   const size_t quads_before = quads_.size();
   auto undo = [&]() {
     quads_.resize(quads_before);
@@ -994,7 +1072,7 @@ bool Compiler::flat_program(const std::vector<uint32_t>& lin, std::vector<FlatQu
     if (etype(op) == E_QUAD) {
       Q q;
       if (!quad_of(op, -1, q)) return undo();
-      add_quad(q, zero);
+      pend.push_back({q, {0, 0, 0}, 0, false});
       continue;
     }
     if (etype(op) != E_INSTANCE) return undo();
@@ -1035,13 +1113,20 @@ bool Compiler::flat_program(const std::vector<uint32_t>& lin, std::vector<FlatQu
         b.face[f] = mk(E_QUAD, (uint32_t)quads_.size() - 1);
       }
       boxes.push_back(b);
-    } else
-      for (const Q& q : qs) add_quad(q, off);
+    } else {
+      for (const Q& q : qs) pend.push_back({q, {off[0], off[1], off[2]}, pools, false});
+      pools++;
+    }
   }
+  for (int p = 0; p < pools; p++) find_rooms(p);
+  for (const Pending& p : pend) add_quad(p.q, p.off, p.in_room);
   quads.clear();
+  quads_all.clear();
   for (int a = 0; a < 3; a++) {
     nq[a] = (uint32_t)grp[a].size();
     quads.insert(quads.end(), grp[a].begin(), grp[a].end());
+    nq_all[a] = (uint32_t)grp_all[a].size();
+    quads_all.insert(quads_all.end(), grp_all[a].begin(), grp_all[a].end());
   }
   return true;
 }
@@ -1567,12 +1652,17 @@ bool Compiler::run(CompiledScene* out, std::string* err) {
   // the flat program of both blobs, when the linear program has that form (may add quad records)
   std::vector<FlatQuadT<double>> fq;
   std::vector<FlatBoxT<double>> fb;
-  uint32_t nq[3] = {0, 0, 0};
+  std::vector<FlatRoomT<double>> fr;
+  std::vector<FlatQuadT<double>> fq_all;  // the quad groups with the rooms' faces still in them
+  uint32_t nq[3] = {0, 0, 0}, nq_all[3] = {0, 0, 0};
   out->desc_quads = (int)quads_.size();
-  const bool has_flat = lin_top.lin_ok && !lin_top.lin.empty() && flat_program(lin_top.lin, fq, nq, fb);
+  const bool has_flat =
+      lin_top.lin_ok && !lin_top.lin.empty() && flat_program(lin_top.lin, fq, nq, fb, fr, fq_all, nq_all);
   if (has_flat) {
-    for (const FlatQuadT<double>& q : fq) out->flat_quads += q.inst != -2;
+    out->flat_quads = (int)fq_all.size();  // a room's walls count as the quads they are
     out->flat_boxes = (int)fb.size();
+    out->flat_rooms = (int)fr.size();
+    for (const FlatRoomT<double>& r : fr) out->room_masks.push_back(r.present);
   }
   out->stack_need = std::max(1, root.need);
   out->bvh_depth = root.depth;
@@ -1590,8 +1680,21 @@ bool Compiler::run(CompiledScene* out, std::string* err) {
   if (has_flat) {
     std::vector<FlatQuadT<float>> fq32;
     std::vector<FlatBoxT<float>> fb32;
-    for (const FlatQuadT<double>& q : fq)
+    std::vector<FlatRoomT<float>> fr32;
+    for (const FlatQuadT<double>& q : kFlatRoomsF32 ? fq : fq_all)
       fq32.push_back({(float)q.plane, (float)q.lo_u, (float)q.lo_w, (float)q.inv_u, (float)q.inv_w, q.e, q.inst, q.nm});
+    for (const FlatRoomT<double>& b : fr) {
+      if (!kFlatRoomsF32) break;
+      FlatRoomT<float> r{};
+      for (int k = 0; k < 3; k++) {
+        r.lo[k] = (float)b.lo[k];
+        r.hi[k] = (float)b.hi[k];
+      }
+      r.inst = b.inst;
+      r.present = b.present;
+      for (int f = 0; f < 6; f++) r.e[f] = b.e[f], r.nm[f] = b.nm[f];
+      fr32.push_back(r);
+    }
     for (const FlatBoxT<double>& b : fb) {
       FlatBoxT<float> r{};
       for (int k = 0; k < 3; k++) {
@@ -1604,17 +1707,24 @@ bool Compiler::run(CompiledScene* out, std::string* err) {
       r.neg = b.neg;
       fb32.push_back(r);
     }
-    auto put = [&](std::vector<unsigned char>& blob, SceneHeader& h, const auto& q, const auto& b) {
+    auto put = [&](std::vector<unsigned char>& blob, SceneHeader& h, const auto& q, const uint32_t* n, const auto& b,
+                   const auto& r) {
       h.off_flat_quad = append(blob, q);
-      h.off_flat_box = append(blob, b);
+      // boxes and rooms as one array of bytes: the rooms start where the boxes end (rt_types.h flat_rooms)
+      std::vector<unsigned char> br(b.size() * sizeof(b[0]) + r.size() * sizeof(r[0]));
+      if (!b.empty()) memcpy(br.data(), b.data(), b.size() * sizeof(b[0]));
+      if (!r.empty()) memcpy(br.data() + b.size() * sizeof(b[0]), r.data(), r.size() * sizeof(r[0]));
+      h.off_flat_box = append(blob, br);
+      h.off_flat_room = h.off_flat_box + b.size() * sizeof(b[0]);
       blob.resize((blob.size() + 255) & ~size_t(255));
       h.bytes = blob.size();
-      for (int a = 0; a < 3; a++) h.n_flat_quad[a] = nq[a];
+      for (int a = 0; a < 3; a++) h.n_flat_quad[a] = n[a];
       h.n_flat_box = (uint32_t)b.size();
+      h.n_flat_room = (uint32_t)r.size();
       h.has_flat = 1;
     };
-    put(out->blob32, out->hdr, fq32, fb32);
-    put(out->blob64, out->hdr64, fq, fb);
+    put(out->blob32, out->hdr, fq32, kFlatRoomsF32 ? nq : nq_all, fb32, fr32);
+    put(out->blob64, out->hdr64, fq, nq, fb, fr);
   }
   // the query tables: (object, that object's material) per record, quads | spheres | triangles | volumes
   out->ids.clear();

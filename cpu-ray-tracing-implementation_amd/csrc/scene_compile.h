@@ -21,7 +21,9 @@ struct CompiledScene {
   int bvh_depth = 0;
   int num_items = 0;
   int desc_quads = 0;  // quads of the descriptor (the flat program adds face copies)
-  int flat_quads = 0, flat_boxes = 0;
+  int flat_quads = 0, flat_boxes = 0;  // flat_quads counts the faces of rooms too (they are the scene's quads)
+  int flat_rooms = 0;                  // rooms of the fp64 flat program (rt_scene.h FlatRoomT)
+  std::vector<uint32_t> room_masks;    // their present masks
   // For ray queries (rt_trace_rays), outside the blobs (the render kernels never read it): the descriptor object
   // behind every device record and that object's rt_object.material, as (object, material) pairs -- the quad
   // records first (the flat program's face copies and its alignment padding included: same indices as the blob),
