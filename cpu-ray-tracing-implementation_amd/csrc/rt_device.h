@@ -115,6 +115,21 @@ __device__ __forceinline__ double fsqrt01(double x) {
   return x > 0.0 ? g : 0.0;
 }
 __device__ __forceinline__ float fsqrt01(float x) { return fsqrt(x); }
+// the same for x in (0, 1], where the zero check is dead: the same bits as fsqrt01 without its compare and two selects
+__device__ __forceinline__ double fsqrt01_nz(double x) {
+  const double r = __builtin_amdgcn_rsq(x);
+  double g = x * r, h = 0.5 * r;
+  const double e = fma(-g, h, 0.5);
+  g = fma(g, e, g);
+  h = fma(h, e, h);
+  return fma(fma(-g, g, x), h, g);
+}
+__device__ __forceinline__ float fsqrt01_nz(float x) { return fsqrt(x); }
+// s x for s = +-1 (neg: s = -1) as a flip of the sign bit: the product's bits, signed zeros included, for any x that
+// is not a NaN, in one 32-bit instruction where the fp64 product takes a double-rate one
+__device__ __forceinline__ double flip_sign(double x, bool neg) {
+  return __longlong_as_double(__double_as_longlong(x) ^ (neg ? (long long)0x8000000000000000ull : 0ll));
+}
 __device__ __forceinline__ double fsqrt(double x) {
   const double r = __builtin_amdgcn_rsq(x);
   double g = x * r, h = 0.5 * r;
@@ -1701,7 +1716,9 @@ __device__ __forceinline__ RoomHit<R> flat_room_test(const FlatRoomHeadT<R>& b, 
   return room_rule<R>(t0, t1, b.present, tmin);
 }
 // fq / fr / fb: where the hit's record is read at the end (the scene's, or the kernel's LDS copy)
-template <class R>
+// FACE (fp64 only): the box loop keeps the axis an entering ray hits (rt_room.h box_face_rule) in the low two bits of
+// a box's number, 3 for a ray that starts inside, so the resolve at the end repeats the slab test for those alone
+template <class R, bool FACE = false>
 __device__ __forceinline__ void trace_flat(const DevScene<R>& sc, V<R> o, V<R> d, uint32_t excl_e, int32_t excl_i,
                                            R& t_best, uint32_t& e_best, int32_t& i_best, uint32_t& nm,
                                            const FlatQuadT<R>* fq, const FlatRoomT<R>* fr, const FlatBoxT<R>* fb) {
@@ -1734,7 +1751,12 @@ __device__ __forceinline__ void trace_flat(const DevScene<R>& sc, V<R> o, V<R> d
     // tf >= max(tn, tmin) is the first two (round 6: C2 fp64 25.28 -> 25.27 ms/frame, fp32 18.37 -> 18.34, r06g)
     const bool h = (s.tf >= fmax(s.tn, tmin)) & (s.th <= tmax);
     tmax = h ? s.th : tmax;
-    best = h ? (int32_t)(nq + nr8 + k) : best;
+    if constexpr (FACE) {
+      const BoxFaceHit<R> f = box_face_rule<R>(s.t0, s.t1, tmin);
+      best = h ? (int32_t)(nq + nr8 + 4u * k) + (f.enter ? f.axis : 3) : best;
+    } else {
+      best = h ? (int32_t)(nq + nr8 + k) : best;
+    }
   }
   t_best = tmax;
   e_best = kNoHit;
@@ -1758,16 +1780,27 @@ __device__ __forceinline__ void trace_flat(const DevScene<R>& sc, V<R> o, V<R> d
   }
   // the face of the box: the axis whose slab bound is the hit distance (recomputed exactly
   // as in the loop), on the side the ray enters (or leaves, from inside)
-  const FlatBoxT<R>& b = fb[(uint32_t)best - nq - nr8];
-  const Slab<R> s = flat_slab(b, o, inv, tmin, excl_i, xf);
-  const bool enter = s.tn >= tmin;
+  const uint32_t bj = (uint32_t)best - nq - nr8;
+  const FlatBoxT<R>& b = fb[FACE ? bj >> 2 : bj];
+  bool enter;
   int k = 2;
-  if (enter) {
-    if (s.tn == fmin(s.t0[0], s.t1[0])) k = 0;
-    else if (s.tn == fmin(s.t0[1], s.t1[1])) k = 1;
+  if constexpr (FACE) {
+    enter = (bj & 3u) != 3u;
+    k = (int)(bj & 3u);
+    if (!enter) {
+      const Slab<R> s = flat_slab(b, o, inv, tmin, excl_i, xf);
+      k = box_face_rule<R>(s.t0, s.t1, tmin).axis;
+    }
   } else {
-    if (s.tf == fmax(s.t0[0], s.t1[0])) k = 0;
-    else if (s.tf == fmax(s.t0[1], s.t1[1])) k = 1;
+    const Slab<R> s = flat_slab(b, o, inv, tmin, excl_i, xf);
+    enter = s.tn >= tmin;
+    if (enter) {
+      if (s.tn == fmin(s.t0[0], s.t1[0])) k = 0;
+      else if (s.tn == fmin(s.t0[1], s.t1[1])) k = 1;
+    } else {
+      if (s.tf == fmax(s.t0[0], s.t1[0])) k = 0;
+      else if (s.tf == fmax(s.t0[1], s.t1[1])) k = 1;
+    }
   }
   const R dk = k == 0 ? d.x : (k == 1 ? d.y : d.z);
   const int side = enter ? (dk < R(0) ? 1 : 0) : (dk < R(0) ? 0 : 1);
@@ -1973,16 +2006,17 @@ __device__ __forceinline__ V<R> on_sphere(R u1, R u2) {
   return on_sphere_sc(u1, sp, cp);
 }
 // random_cosine_direction (utility.h:61-69)
-template <class R>
+// DRAW: r2 is a draw (to_unit: a 24-bit value below 1), so 1 - r2 >= 2^-24 and its root needs no zero check
+template <class R, bool DRAW = false>
 __device__ __forceinline__ V<R> cosine_dir_sc(R r2, R sp, R cp) {
   R sr2 = fsqrt01(r2);
-  return mkv(cp * sr2, fsqrt01(R(1) - r2), sp * sr2);
+  return mkv(cp * sr2, DRAW ? fsqrt01_nz(R(1) - r2) : fsqrt01(R(1) - r2), sp * sr2);
 }
-template <class R>
+template <class R, bool DRAW = false>
 __device__ __forceinline__ V<R> cosine_dir(R r1, R r2) {
   R sp, cp;
   sincos2pi(r1, sp, cp);
-  return cosine_dir_sc(r2, sp, cp);
+  return cosine_dir_sc<R, DRAW>(r2, sp, cp);
 }
 
 // hittable_pdf over the light (hittable_list.h:39-50 -> quad.h:66-78 / sphere.h:76-81 / hittable.h:39-41)

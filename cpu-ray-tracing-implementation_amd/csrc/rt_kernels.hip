@@ -18,6 +18,7 @@
 #include <map>
 #include <mutex>
 #include <tuple>
+#include <type_traits>
 
 #include "../../include/rt_hip.h"
 #include "rt_device.h"
@@ -727,8 +728,13 @@ __device__ bool shade(const Params<R>& p, PS& s, R t, uint32_t e, int32_t inst, 
         // values without the cross products and the nine multiply-adds (signed zeros aside, which no
         // later test can tell apart); dot(u, n) is fs u_A
         auto cos_dir = [&](R u1, R u2) -> V<R> {
-          const V<R> v = cosine_dir(u1, u2);
-          if constexpr (FLAT) {
+          // (the flat LL kernels: u2 is a draw, so sqrt(1 - u2) needs no zero check; fp64: fs v as a sign flip. Both
+          // leave every bit as it was; the other kernels that shade with this code keep theirs)
+          const V<R> v = cosine_dir<R, FLAT && LL>(u1, u2);
+          if constexpr (FLAT && LL && sizeof(R) == 8) {
+            const R sy = flip_sign(v.y, fs < R(0)), sz = flip_sign(v.z, fs < R(0));
+            return fA == 0 ? mkv(sy, -sz, -v.x) : (fA == 1 ? mkv(-v.x, sy, -sz) : mkv(-v.x, sz, sy));
+          } else if constexpr (FLAT) {
             const R sy = fs * v.y, sz = fs * v.z;
             return fA == 0 ? mkv(sy, -sz, -v.x) : (fA == 1 ? mkv(-v.x, sy, -sz) : mkv(-v.x, sz, sy));
           } else {
@@ -895,6 +901,9 @@ struct TravDefaults {
   [[maybe_unused]] static constexpr bool kLL = false, kNL = false, kLLI = false, kMoving = true;
   // the path state (Path): lean, no radiance register, cold fields in LDS, throughput in LDS
   [[maybe_unused]] static constexpr bool kLean = false, kNoRad = false, kColdLds = false, kThrLds = false;
+  // the segment loop tests the segment cap between trace and shade, as every kernel did before round 9, instead of
+  // after shade (persist_body)
+  static constexpr bool kCapBeforeShade = false;
 };
 template <class R, bool SPH, bool TRI, bool VOL, bool LLI = false>
 struct LinearTrav : TravDefaults {
@@ -910,6 +919,9 @@ struct LinearTrav : TravDefaults {
   static constexpr bool kNoRad = VOL;
   static constexpr bool kColdLds = VOL;
   static constexpr bool kThrLds = VOL && LLI && sizeof(R) == 4;  // (Path LT: C5 fp32 1,091 -> 1,072 ms/frame, r06d)
+  // the fp32 LLI kernel keeps the cap test where it was: with it after shade the kernel spilled 24 B in place of 16
+  // and C5 fp32 went 1,071 -> 1,078 ms/frame (round 9)
+  static constexpr bool kCapBeforeShade = VOL && LLI && sizeof(R) == 4;
   template <class PS>
   __device__ __forceinline__ static void run(const DevScene<R>& sc, const Node<R>*, const PS& s, Keys k,
                                              uint32_t*, R& t, uint32_t& e, int32_t& i, uint32_t&) {
@@ -978,7 +990,7 @@ struct FlatTrav : TravDefaults {
   template <class PS>
   __device__ __forceinline__ static void run_lds(const DevScene<R>& sc, const Tables& tb, const PS& s, R& t,
                                                  uint32_t& e, int32_t& i, uint32_t& nm) {
-    trace_flat<R>(sc, s.o, s.d, s.xe, s.xi, t, e, i, nm, tb.q, tb.r, tb.b);
+    trace_flat<R, sizeof(R) == 8>(sc, s.o, s.d, s.xe, s.xi, t, e, i, nm, tb.q, tb.r, tb.b);
   }
 };
 // LDSN: the scene's BVH nodes (at most kLdsNodeMax) are copied into LDS at kernel start, so
@@ -1217,6 +1229,18 @@ __device__ __forceinline__ bool seg_cap_hit(const Params<R>& q, uint64_t segs) {
   }
   return false;
 }
+// The same for the loops that count in 32 bits (launch keeps seg_cap below 2^32): the count is the loop's iteration
+// number, the same in every lane still in it, so the compare is one scalar instruction
+// (p: the kernel's own parameter, for the fault word's address. The compiler sinks the store below the loop, and an
+// address read through q, which is a new value every iteration, would be copied into a VGPR pair every iteration)
+template <class R>
+__device__ __forceinline__ bool seg_cap_hit(const Params<R>& p, const Params<R>& q, uint32_t segs) {
+  if (segs > (uint32_t)q.seg_cap) {
+    atomicOr(p.fault, 1u);
+    return true;
+  }
+  return false;
+}
 template <class R, class Trav, bool CAMX>
 __device__ __forceinline__ void persist_body(const Params<R>& p) {
   __shared__ Lds<Trav::kStack * kBlock> stk;
@@ -1270,7 +1294,7 @@ __device__ __forceinline__ void persist_body(const Params<R>& p) {
     }
     item0 = next_item_dyn(p);
   }
-  uint64_t segs = 0;
+  std::conditional_t<Trav::kWide || Trav::kCapBeforeShade, uint64_t, uint32_t> segs = 0;
   if (item0 < p.n_items) {
     Path<R, Trav::kColdLds, Trav::kLean, Trav::kNoRad, Trav::kThrLds> s;
     s.set_acc(mkv(R(0), R(0), R(0)));
@@ -1305,8 +1329,17 @@ __device__ __forceinline__ void persist_body(const Params<R>& p) {
           RT_WAVE_TIMED(6, Trav::run_lds(q.sc, *flat_tb, s, t, e, inst, nm));
         else
           RT_WAVE_TIMED(6, Trav::run(q.sc, trav_nodes, s, Keys{s.ks}, stk_lane, t, e, inst, nm));
-        if (seg_cap_hit(q, ++segs)) break;
+        // The segment is counted before shade (a lane that shade retires has traced it) and the cap tested after:
+        // tested between trace and shade, the cap's exit was a second edge out of the loop that carried the path state
+        // the iteration began with, and the loop's latch copied the state shade wrote over it, every iteration
+        // (DESIGN.md §4, round 9). A lane past its cap, which cannot happen, shades once more before it leaves
+        // (Trav::kCapBeforeShade: the one kernel that was slower so keeps the earlier order, and its 64-bit count)
+        ++segs;
+        if constexpr (Trav::kCapBeforeShade)
+          if (seg_cap_hit(q, segs)) break;
         if (!RT_WAVE_TIMED(7, shade<R, CAMX, ShadeOf<Trav>>(q, s, t, e, inst, nm, mats, lm))) break;
+        if constexpr (!Trav::kCapBeforeShade)
+          if (seg_cap_hit(p, q, segs)) break;
       }
     }
   }
@@ -1885,7 +1918,8 @@ void launch_one(KernelT kern, Params<R> p, uint32_t grid, hipStream_t st, size_t
     const uint32_t res = hipGetDevice(&dev) == hipSuccess ? resident_blocks((const void*)kern, dev, lds) : 0;
     if (res > 0) grid = std::min<uint32_t>(grid, res);
     p.P = grid * kBlock;
-    p.seg_cap = (uint64_t)p.n_items * p.chunk * (uint64_t)p.max_depth + 1;
+    // (at most UINT32_MAX: the flat, linear and binary-BVH loops count a lane's segments in 32 bits)
+    p.seg_cap = std::min<uint64_t>((uint64_t)p.n_items * p.chunk * (uint64_t)p.max_depth + 1, UINT32_MAX);
     t_grid_lanes = (uint64_t)grid * kBlock;
   }
   hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), lds, st, p);

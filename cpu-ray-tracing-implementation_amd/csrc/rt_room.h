@@ -82,4 +82,31 @@ __host__ __device__ inline RoomHit<R> room_rule(const R t0[3], const R t1[3], ui
   return r;
 }
 
+// The face of a closed box (flat_slab's rule, rt_device.h) from the same six distances: the hit is tn through the
+// face the ray enters by when tn >= tmin, else tf through the face it leaves by (a ray that starts inside). The
+// axis is the first of x, y, z whose near (far) distance is tn (tf) bit for bit, z when neither x nor y is: at an
+// edge or a corner, where two or three are equal, the first wins, and a NaN distance equals nothing. Which of the
+// axis's two planes it is the caller reads from the sign of the direction. trace_flat's box loop and its resolve
+// both call this (the loop keeps the axis of an entering hit, so the resolve computes nothing for it), and
+// tests/native/box_face_rule.cpp compares it with the resolve written out.
+template <class R>
+struct BoxFaceHit {
+  R t;         // tn or tf (the caller tests tf >= max(tn, tmin) and t <= tmax)
+  int axis;    // 0, 1, 2
+  bool enter;  // tn >= tmin
+};
+template <class R>
+__host__ __device__ inline BoxFaceHit<R> box_face_rule(const R t0[3], const R t1[3], R tmin) {
+  const R n0 = fmin(t0[0], t1[0]), n1 = fmin(t0[1], t1[1]), n2 = fmin(t0[2], t1[2]);
+  const R f0 = fmax(t0[0], t1[0]), f1 = fmax(t0[1], t1[1]), f2 = fmax(t0[2], t1[2]);
+  const R tn = fmax(fmax(n0, n1), n2);
+  const R tf = fmin(fmin(f0, f1), f2);
+  BoxFaceHit<R> r;
+  r.enter = tn >= tmin;
+  r.t = r.enter ? tn : tf;
+  const int an = tn == n0 ? 0 : (tn == n1 ? 1 : 2), af = tf == f0 ? 0 : (tf == f1 ? 1 : 2);
+  r.axis = r.enter ? an : af;
+  return r;
+}
+
 }  // namespace rtd
