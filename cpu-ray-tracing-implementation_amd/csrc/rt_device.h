@@ -843,12 +843,16 @@ __device__ bool volume_t(const DevScene<R>& sc, const Volume<R>& v, V<R> wo, V<R
 __device__ unsigned long long g_trace_totals[3];
 #define g_trace_counts tc
 #endif
-template <class R, int STACK, int BLOCK>
+// ANY (rt_occluded, a scene rt_plan.h occlusion_early_exit accepts: no volumes, no fp64 quad records beside fp32 rays):
+// t_best comes in as the upper end of the interval, and the lane empties its stack at the first primitive that
+// accepts; e_best != kNoHit then says "occluded" and nothing else of the hit is kept.
+template <class R, int STACK, int BLOCK, bool ANY = false>
 __device__ void trace(const DevScene<R>& sc, const Node<R>* nodes, V<R> wo, V<R> wd, R time, uint32_t excl_e,
                       int32_t excl_i, Keys keys, uint32_t bounce, uint32_t xy, uint32_t* stk, R& t_best, uint32_t& e_best,
                       int32_t& i_best) {
   const R tmin = R(0.001);
   R tmax = Num<R>::inf();
+  if constexpr (ANY) tmax = t_best;
   V<R> o = wo, d = wd;
   V<R> inv = box_inv(d);
   int32_t cur = -1;
@@ -874,7 +878,10 @@ __device__ void trace(const DevScene<R>& sc, const Node<R>* nodes, V<R> wo, V<R>
     bool h;
     if (ty == E_QUAD) {
       if (self) return;
-      h = quad_t_near(sc, i, o, d, tmin, tmax, th, EdgeRay{keys.ks, xy, bounce}, cur < 0);
+      if constexpr (ANY)  // (no fp64 quad records here: quad_t_near would be this test)
+        h = quad_t(sc.quads[i], o, d, tmin, tmax, th);
+      else
+        h = quad_t_near(sc, i, o, d, tmin, tmax, th, EdgeRay{keys.ks, xy, bounce}, cur < 0);
     } else if (ty == E_SPHERE) {
       h = sphere_t(sc.spheres[i], o, d, time, tmin, tmax, self, th);
     } else {
@@ -885,14 +892,17 @@ __device__ void trace(const DevScene<R>& sc, const Node<R>* nodes, V<R> wo, V<R>
       tmax = th;
       e_best = e;
       i_best = cur;
+      if constexpr (ANY) sp = 0;  // the first accepted hit ends the ray
     }
   };
   auto test_volume = [&](uint32_t e) {
-    R th;
-    if (volume_t(sc, sc.vols[epay(e)], wo, wd, d, time, tmin, tmax, keys, bounce, jv, th)) {
-      tmax = th;
-      e_best = e;
-      i_best = cur;
+    if constexpr (!ANY) {
+      R th;
+      if (volume_t(sc, sc.vols[epay(e)], wo, wd, d, time, tmin, tmax, keys, bounce, jv, th)) {
+        tmax = th;
+        e_best = e;
+        i_best = cur;
+      }
     }
   };
 
@@ -940,6 +950,8 @@ __device__ void trace(const DevScene<R>& sc, const Node<R>* nodes, V<R> wo, V<R>
         uint32_t rt = etype(r);
         if (rt <= E_TRI) {
           test_prim(r);
+          if constexpr (ANY)
+            if (e_best != kNoHit) break;
         } else if (rt == E_VOLUME) {
           test_volume(r);
         } else {
@@ -1043,7 +1055,9 @@ using WStackT = typename std::conditional<LDSN, uint16_t, uint32_t>::type;
 // being covered, like the fp32 path's own, by the relative box_slack of the exit distance; the
 // lower bound is 0.00099 instead of 0.001. The boxes only cull: the primitive tests are the fp64
 // ones of the other fp64 traversals, so the closest hit is theirs (exact-t ties aside).
-template <class R, bool SPH, bool TRI, bool QUAD, bool MOV, bool LDSN, int BLOCK, int PAUSE>
+// ANY (rt_occluded): ry.tmax starts as the upper end of the interval instead of +inf, and the ray is finished at the
+// first primitive that accepts (ry.e != kNoHit: occluded); its stack is simply dropped.
+template <class R, bool SPH, bool TRI, bool QUAD, bool MOV, bool LDSN, int BLOCK, int PAUSE, bool ANY = false>
 __device__ __forceinline__ bool trace_wide(const DevScene<R>& sc, const unsigned char* lds_nodes,
                                            const typename WWord<R>::T* lds_prims, V<R> ro, V<R> rd, R time,
                                            uint32_t excl_e, WStackT<LDSN>* stk, WideRayT<R>& ry) {
@@ -1346,6 +1360,7 @@ __device__ __forceinline__ bool trace_wide(const DevScene<R>& sc, const unsigned
       if (hit) {
         tmax = th;
         e_best = e;
+        if constexpr (ANY) return;
       }
     }
   };
@@ -1357,6 +1372,12 @@ __device__ __forceinline__ bool trace_wide(const DevScene<R>& sc, const unsigned
   if (ry.fresh) {  // every lane alike: no divergence, and the tree starts bounded by their hit
     test_prims(0u, sc.wide_big);
     ry.fresh = 0;
+    if constexpr (ANY) {
+      if (e_best != kNoHit) {
+        ry.e = e_best;
+        return true;
+      }
+    }
   }
   bool done = false;
   // Speculative while-while (Aila & Laine 2009), for trees in HBM: a lane that reaches a leaf
@@ -1445,6 +1466,12 @@ __device__ __forceinline__ bool trace_wide(const DevScene<R>& sc, const unsigned
     if (leaf)
       test_prims(LDSN ? (leaf & 0xFFFu) : (leaf & kWFirstMask),
                  (LDSN ? ((leaf >> 12) & 7u) : ((leaf >> kWCountShift) & 63u)) + 1u);
+    if constexpr (ANY) {
+      if (e_best != kNoHit) {
+        done = true;
+        break;
+      }
+    }
     if (!have) {
       done = true;
       break;
@@ -1510,6 +1537,12 @@ __device__ __forceinline__ bool trace_wide(const DevScene<R>& sc, const unsigned
     if (done) break;
     test_prims(LDSN ? (cur & 0xFFFu) : (cur & kWFirstMask),
                (LDSN ? ((cur >> 12) & 7u) : ((cur >> kWCountShift) & 63u)) + 1u);
+    if constexpr (ANY) {
+      if (e_best != kNoHit) {
+        done = true;
+        break;
+      }
+    }
     if (sp == 0) {
       done = true;
       break;
@@ -1529,12 +1562,15 @@ __device__ __forceinline__ bool trace_wide(const DevScene<R>& sc, const unsigned
 
 // Linear program (small scenes, rt_scene.h): every lane walks the same ops, so
 // the loop, the op and the primitive records are wave-uniform (scalar loads).
-template <class R, bool SPH, bool TRI, bool VOL>
+// ANY (rt_occluded, a scene without volumes): t_best comes in as the upper end of the interval, e_best != kNoHit
+// says "occluded", and the wave leaves the op loop once every lane of it holds a hit.
+template <class R, bool SPH, bool TRI, bool VOL, bool ANY = false>
 __device__ __forceinline__ void trace_linear(const DevScene<R>& sc, V<R> wo, V<R> wd, R time, uint32_t excl_e,
                                              int32_t excl_i, Keys keys, uint32_t bounce, R& t_best,
                                              uint32_t& e_best, int32_t& i_best) {
   const R tmin = R(0.001);
   R tmax = Num<R>::inf();
+  if constexpr (ANY) tmax = t_best;
   V<R> o = wo, d = wd;
   // fp32: v_rcp_f32 once per ray and instance (fp64 divides per quad: per-ray refined reciprocals were
   // neutral at 3 waves and cost 24 VGPRs)
@@ -1586,7 +1622,7 @@ __device__ __forceinline__ void trace_linear(const DevScene<R>& sc, V<R> wo, V<R
         d = op_in(x, d, false);
       }
       inv = rcp3(d);
-    } else if (VOL && ty == E_VOLUME) {
+    } else if (VOL && !ANY && ty == E_VOLUME) {
       const Volume<R> vol = ld_uniform(sc.vols, idx);
       h = volume_t<R, true>(sc, vol, wo, wd, d, time, tmin, tmax, keys, bounce, jv, th);
     } else {  // kInstEnd
@@ -1601,6 +1637,8 @@ __device__ __forceinline__ void trace_linear(const DevScene<R>& sc, V<R> wo, V<R
       e_best = op;
       i_best = cur;
     }
+    if constexpr (ANY)
+      if (__ballot(e_best == kNoHit) == 0ull) break;
   }
   t_best = tmax;
 }
@@ -1718,7 +1756,9 @@ __device__ __forceinline__ RoomHit<R> flat_room_test(const FlatRoomHeadT<R>& b, 
 // fq / fr / fb: where the hit's record is read at the end (the scene's, or the kernel's LDS copy)
 // FACE (fp64 only): the box loop keeps the axis an entering ray hits (rt_room.h box_face_rule) in the low two bits of
 // a box's number, 3 for a ray that starts inside, so the resolve at the end repeats the slab test for those alone
-template <class R, bool FACE = false>
+// ANY (rt_occluded): t_best comes in as the upper end of the interval and e_best != kNoHit says "occluded" (no
+// record is resolved); the wave leaves between the quad groups, the rooms and the boxes once all its lanes hold a hit.
+template <class R, bool FACE = false, bool ANY = false>
 __device__ __forceinline__ void trace_flat(const DevScene<R>& sc, V<R> o, V<R> d, uint32_t excl_e, int32_t excl_i,
                                            R& t_best, uint32_t& e_best, int32_t& i_best, uint32_t& nm,
                                            const FlatQuadT<R>* fq, const FlatRoomT<R>* fr, const FlatBoxT<R>* fb) {
@@ -1729,6 +1769,40 @@ __device__ __forceinline__ void trace_flat(const DevScene<R>& sc, V<R> o, V<R> d
   const uint32_t xf = excl_e & 7u;
   int32_t best = -1;
   const uint32_t n0 = sc.n_flatq[0], n1 = sc.n_flatq[1], n2 = sc.n_flatq[2], nq = n0 + n1 + n2;
+  if constexpr (ANY) {
+    tmax = t_best;
+    auto all_hit = [&]() { return __ballot(best < 0) == 0ull; };
+    auto walk = [&]() {
+      flat_quads<0>(sc.flatq, n0, 0, o, d, inv, tmin, tmax, best, xkey);
+      if (all_hit()) return;
+      flat_quads<1>(sc.flatq + n0, n1, (int32_t)n0, o, d, inv, tmin, tmax, best, xkey);
+      if (all_hit()) return;
+      flat_quads<2>(sc.flatq + n0 + n1, n2, (int32_t)(n0 + n1), o, d, inv, tmin, tmax, best, xkey);
+      if (all_hit()) return;
+      const uint32_t nr = (sizeof(R) == 8 || kFlatRoomsF32) ? sc.n_flatr : 0u;
+      const FlatRoomT<R>* rooms = flat_rooms(sc);
+#pragma unroll 1
+      for (uint32_t k = 0; k < nr; k++) {
+        const FlatRoomHeadT<R> b = ld_scalar(reinterpret_cast<const FlatRoomHeadT<R>*>(rooms + k));
+        const RoomHit<R> r = flat_room_test(b, o, inv, tmin, excl_e, excl_i);
+        if (r.hit & (r.t <= tmax)) best = 0;
+        if (all_hit()) return;
+      }
+#pragma unroll 1
+      for (uint32_t k = 0; k < sc.n_flatb; k++) {
+        const FlatBoxT<R> b = ld_scalar(sc.flatb + k);
+        const Slab<R> s = flat_slab(b, o, inv, tmin, excl_i, xf);
+        if ((s.tf >= fmax(s.tn, tmin)) & (s.th <= tmax)) best = 0;
+        if (all_hit()) return;
+      }
+    };
+    walk();
+    t_best = tmax;
+    e_best = best < 0 ? kNoHit : 0u;
+    i_best = -1;
+    nm = 0;
+    return;
+  }
   flat_quads<0>(sc.flatq, n0, 0, o, d, inv, tmin, tmax, best, xkey);
   flat_quads<1>(sc.flatq + n0, n1, (int32_t)n0, o, d, inv, tmin, tmax, best, xkey);
   flat_quads<2>(sc.flatq + n0 + n1, n2, (int32_t)(n0 + n1), o, d, inv, tmin, tmax, best, xkey);

@@ -922,10 +922,11 @@ struct LinearTrav : TravDefaults {
   // the fp32 LLI kernel keeps the cap test where it was: with it after shade the kernel spilled 24 B in place of 16
   // and C5 fp32 went 1,071 -> 1,078 ms/frame (round 9)
   static constexpr bool kCapBeforeShade = VOL && LLI && sizeof(R) == 4;
-  template <class PS>
+  // ANY (here and in the other policies): the any-hit form of the traversal, rt_occluded's (rt_device.h)
+  template <bool ANY = false, class PS>
   __device__ __forceinline__ static void run(const DevScene<R>& sc, const Node<R>*, const PS& s, Keys k,
                                              uint32_t*, R& t, uint32_t& e, int32_t& i, uint32_t&) {
-    trace_linear<R, SPH, TRI, VOL>(sc, s.o, s.d, s.tm, s.xe, s.xi, k, (uint32_t)s.bounce, t, e, i);
+    trace_linear<R, SPH, TRI, VOL, ANY>(sc, s.o, s.d, s.tm, s.xe, s.xi, k, (uint32_t)s.bounce, t, e, i);
   }
 };
 // The flat program (quad/box scenes such as every Cornell config): rt_device.h trace_flat.
@@ -948,10 +949,10 @@ struct FlatTrav : TravDefaults {
   // not lean (fp32: 72 -> 64 VGPRs, but C2 23.5 -> 24.1 ms/frame)
   static constexpr bool kNoRad = true;  // 6 VGPRs in fp64 (its item sum is in LDS)
   static constexpr bool kColdLds = sizeof(R) == 8;
-  template <class PS>
+  template <bool ANY = false, class PS>
   __device__ __forceinline__ static void run(const DevScene<R>& sc, const Node<R>*, const PS& s, Keys, uint32_t*,
                                              R& t, uint32_t& e, int32_t& i, uint32_t& nm) {
-    trace_flat<R>(sc, s.o, s.d, s.xe, s.xi, t, e, i, nm, sc.flatq, flat_rooms(sc), sc.flatb);
+    trace_flat<R, false, ANY>(sc, s.o, s.d, s.xe, s.xi, t, e, i, nm, sc.flatq, flat_rooms(sc), sc.flatb);
   }
   // the scene's small tables copied into LDS (persistent kernel): the hit's record and
   // material are then LDS reads instead of dependent global loads
@@ -1001,11 +1002,11 @@ struct StackTrav : TravDefaults {  // (no cold state in LDS: its LDS holds the t
   static constexpr int kStack = STACK;
   static constexpr int kLdsNodes = LDSN ? (int)kLdsNodeMax : 0;
   static constexpr int kWaves = sizeof(R) == 4 ? RT_STACK_WAVES : (LDSN ? 1 : RT_STACK_WAVES_F64);  // occupancy over a small spill
-  template <class PS>
+  template <bool ANY = false, class PS>
   __device__ __forceinline__ static void run(const DevScene<R>& sc, const Node<R>* nodes, const PS& s, Keys k,
                                              uint32_t* stk, R& t, uint32_t& e, int32_t& i, uint32_t&) {
-    trace<R, STACK, kBlock>(sc, LDSN ? nodes : sc.nodes, s.o, s.d, s.tm, s.xe, s.xi, k, (uint32_t)s.bounce, s.xy(),
-                            stk, t, e, i);
+    trace<R, STACK, kBlock, ANY>(sc, LDSN ? nodes : sc.nodes, s.o, s.d, s.tm, s.xe, s.xi, k, (uint32_t)s.bounce,
+                                 s.xy(), stk, t, e, i);
   }
 };
 
@@ -1100,12 +1101,12 @@ struct WideTrav : TravDefaults {  // (no cold state in LDS: its LDS holds the tr
     return (StackT*)(base + stack_offset(sc.n_wnodes, sc.n_wprim_words));
   }
   // Advance the ray of s (false: paused, see trace_wide)
-  template <class PS>
+  template <bool ANY = false, class PS>
   __device__ __forceinline__ static bool steps(const DevScene<R>& sc, const Node<R>* lds, const PS& s, StackT* stk,
                                                WideRayT<R>& ry) {
     const unsigned char* base = (const unsigned char*)lds;
     // LDSN: the whole tree at the base; kTop: the copy of the tree's first levels after the stack
-    return trace_wide<R, SPH, TRI, QUAD, MOV, LDSN, kBlock, LDSN ? RT_SHADE_BATCH : RT_SHADE_BATCH_GLOBAL>(
+    return trace_wide<R, SPH, TRI, QUAD, MOV, LDSN, kBlock, LDSN ? RT_SHADE_BATCH : RT_SHADE_BATCH_GLOBAL, ANY>(
         sc, (kTop || kTopH) ? base + top_offset(sc.wide_stack) : base, (const WW*)(base + sc.n_wnodes * kWNodeLdsStride), s.o,
         s.d, s.tm, s.xe, stk, ry);
   }
@@ -1493,8 +1494,8 @@ __device__ __forceinline__ void hit_record(const DevScene<R>& sc, V<R> o, V<R> d
   }
 }
 
-template <class R>
-__device__ __forceinline__ void load_query(const KTrace<R>& a, uint32_t i, QueryRay<R>& s, double& tmax) {
+template <class R, class A>  // A: KTrace<R> or KOccl<R> (rays, seed)
+__device__ __forceinline__ void load_query(const A& a, uint32_t i, QueryRay<R>& s, double& tmax) {
   const double2* q = (const double2*)(a.rays + 8ull * i);  // 64 bytes, 16-byte aligned
   const double2 r0 = q[0], r1 = q[1], r2 = q[2], r3 = q[3];
   s.o = mkv(R(r0.x), R(r0.y), R(r1.x));
@@ -1537,11 +1538,39 @@ __device__ __forceinline__ void store_query(const KTrace<R>& a, uint32_t i, cons
 // source and the hit sink: valid() says whether the lane has a first ray, load() builds the current one, hit() takes
 // its closest hit, advance() moves on and says whether there is another. k_trace's job reads caller-given rays and
 // writes one record a ray; k_aov's builds the camera rays of a pixel and sums their feature channels.
+// Job::kAny (k_occluded's early-exit job): the traversals run in their any-hit form, the interval's upper end being
+// the job's bound() of the current ray; hit() then takes e != kNoHit as "occluded" and nothing else of a hit.
 template <class R, class Trav, class Job>
 __device__ __forceinline__ void query_loop(const DevScene<R>& sc, Job& job) {
   __shared__ Lds<Trav::kStack * kBlock> stk;
   QueryRay<R> s;
-  if constexpr (Trav::kWide) {
+  if constexpr (Job::kAny && Trav::kWide) {
+    using StackT = typename Trav::StackT;
+    extern __shared__ uint4 dyn_lds[];
+    StackT* wstk = Trav::fill(sc, dyn_lds) + threadIdx.x;  // (every lane of the block: it holds the barriers)
+    if (!job.valid()) return;
+    job.load(s);
+    const uint32_t root = Trav::root(sc);
+    WideRayT<R> ry{root, 0, job.bound(), kNoHit, 1u};
+#pragma unroll 1
+    for (;;) {
+      if (!Trav::template steps<true>(sc, (const Node<R>*)dyn_lds, s, wstk, ry)) continue;
+      job.template hit<false>(s, ry.tmax, ry.e, -1, 0u);
+      if (!job.advance()) break;
+      job.load(s);
+      ry = WideRayT<R>{root, 0, job.bound(), kNoHit, 1u};
+    }
+  } else if constexpr (Job::kAny) {
+#pragma unroll 1
+    for (bool more = job.valid(); more; more = job.advance()) {
+      job.load(s);
+      R t = job.bound();
+      uint32_t e, nm = 0;
+      int32_t inst;
+      Trav::template run<true>(sc, sc.nodes, s, Keys{s.ks}, stk.v + threadIdx.x, t, e, inst, nm);
+      job.template hit<Trav::kFlat>(s, t, e, inst, nm);
+    }
+  } else if constexpr (Trav::kWide) {
     // the resumable traversal, driven as persist_body drives it: a ray paused with the wave's laggards carries on
     // beside the rays the finished lanes take next
     using StackT = typename Trav::StackT;
@@ -1574,6 +1603,7 @@ __device__ __forceinline__ void query_loop(const DevScene<R>& sc, Job& job) {
 
 template <class R>
 struct TraceJob {
+  static constexpr bool kAny = false;
   const KTrace<R>& a;
   uint32_t i, stride;  // stride: at most the resident lanes, so i + stride stays below 2^32
   double tmax;
@@ -1594,6 +1624,60 @@ __global__ __launch_bounds__(kBlock) void k_trace(KTrace<R> a) {
   const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
   if (i == 0) atomicAdd(a.seg_shards, (unsigned long long)a.n);  // rt_counters.segments
   TraceJob<R> job{a, i, gridDim.x * kBlock, 0.0};
+  query_loop<R, Trav>(a.sc, job);
+}
+
+// ------------------------------------------------------------------ occlusion queries (rt_occluded)
+// k_occluded: out[i] = 1 exactly when k_trace reports a hit for ray i (finite t), one byte a ray.
+// EARLY (rt_plan.h occlusion_early_exit): the traversal's interval is [0.001, bound] from the start, bound being the
+// largest R value <= tmax, and the lane is done at the first primitive that accepts -- no hit record, no ids. For a
+// t representable in R, t <= bound <=> (double)t <= tmax, k_trace's own comparison; a primitive's test returns its
+// first root inside the closed interval, so some primitive accepts within [0.001, bound] exactly when the closest
+// hit is <= bound. !EARLY: k_trace's traversal and draws unchanged, then (double)t <= tmax.
+template <class R>
+struct KOccl : OcclParams<R> {};
+
+template <class R, bool EARLY>
+struct OcclJob {
+  static constexpr bool kAny = EARLY;
+  const KOccl<R>& a;
+  uint32_t i, stride;  // as TraceJob's
+  double tmax;
+  R bnd;      // EARLY: the interval's upper end, never below its lower one (the fp32 tests order bit patterns)
+  bool live;  // EARLY: [0.001, tmax] holds an R value at all (false also for a NaN tmax): else the answer is 0
+  __device__ __forceinline__ bool valid() const { return i < a.n; }
+  __device__ __forceinline__ void load(QueryRay<R>& s) {
+    load_query(a, i, s, tmax);
+    if constexpr (EARLY) {
+      R b = (R)tmax;  // fp32: to nearest, then down where that went up (+inf stays, a finite tmax above FLT_MAX
+                      // becomes FLT_MAX; a negative or NaN tmax fails the comparison below whatever its bits)
+      if constexpr (sizeof(R) == 4)
+        if ((double)b > tmax) b = __uint_as_float(__float_as_uint(b) - 1u);
+      live = b >= R(0.001);
+      bnd = live ? b : R(0.001);
+    }
+  }
+  __device__ __forceinline__ R bound() const { return bnd; }
+  template <bool FLAT>
+  __device__ __forceinline__ void hit(const QueryRay<R>&, R t, uint32_t e, int32_t, uint32_t) {
+    bool occ;
+    if constexpr (EARLY)
+      occ = live & (e != kNoHit);
+    else
+      occ = e != kNoHit && (double)t <= tmax;  // store_query's test
+    a.out[i] = occ ? (uint8_t)1 : (uint8_t)0;
+  }
+  __device__ __forceinline__ bool advance() {
+    i += stride;
+    return i < a.n;
+  }
+};
+
+template <class R, class Trav, bool EARLY>
+__global__ __launch_bounds__(kBlock) void k_occluded(KOccl<R> a) {
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  if (i == 0) atomicAdd(a.seg_shards, (unsigned long long)a.n);  // rt_counters.segments
+  OcclJob<R, EARLY> job{a, i, gridDim.x * kBlock, 0.0, R(0), false};
   query_loop<R, Trav>(a.sc, job);
 }
 
@@ -1647,6 +1731,7 @@ struct KAov : AovParams<R> {};
 
 template <class R, bool EXT>
 struct AovJob {
+  static constexpr bool kAny = false;
   const KAov<R>& a;
   uint32_t pix, stride;
   uint32_t sidx, xy, ka;
@@ -2025,6 +2110,10 @@ template <class R, class Trav>
 void launch_trace_k(const KTrace<R>& p, uint32_t max_blocks, hipStream_t st, size_t lds = 0) {
   launch_resident(k_trace<R, Trav>, p, p.n, max_blocks, st, lds);
 }
+template <class R, class Trav, bool EARLY>
+void launch_occl_k(const KOccl<R>& p, uint32_t max_blocks, hipStream_t st, size_t lds = 0) {
+  launch_resident(k_occluded<R, Trav, EARLY>, p, p.n, max_blocks, st, lds);
+}
 template <class R, class Trav>
 void launch_aov_k(const KAov<R>& p, uint32_t max_blocks, hipStream_t st, size_t lds = 0) {
   if (p.ext)
@@ -2128,6 +2217,46 @@ void launch_trace(const TraceParams<R>& tp, TraceFamily fam, hipStream_t st) {
   }
 }
 
+// Occlusion queries: launch_trace's instantiations in their any-hit form, and the closest-hit form of the two
+// families occlusion_early_exit can refuse (the linear program and the binary BVH)
+template <class R>
+void launch_occluded(const OcclParams<R>& op, TraceFamily fam, bool early, hipStream_t st) {
+  const KOccl<R> p{op};
+  constexpr uint32_t kMaxBlocks = 1u << 14;
+  switch (fam) {
+    case TF_FLAT:
+      if constexpr (family_built(KF_FLAT)) launch_occl_k<R, FlatTrav<R>, true>(p, kMaxBlocks, st);
+      return;
+    case TF_LINEAR:
+      if constexpr (family_built(KF_LIN_ALL)) {
+        if (early)
+          launch_occl_k<R, LinearTrav<R, true, true, true>, true>(p, kMaxBlocks, st);
+        else
+          launch_occl_k<R, LinearTrav<R, true, true, true>, false>(p, kMaxBlocks, st);
+      }
+      return;
+    case TF_WIDE_LDS:
+      if constexpr (family_built(KF_WIDE))
+        launch_occl_k<R, WideTrav<R, true, true, true, true, true>, true>(p, kMaxBlocks, st,
+                                                                          wide_lds_bytes(p.sc, true));
+      return;
+    case TF_WIDE_HBM:
+      if constexpr (family_built(KF_WIDE))  // the spill area holds spill_lanes lanes: never launch more
+        launch_occl_k<R, WideTrav<R, true, true, true, true, false>, true>(
+            p, p.sc.wide_spill ? std::min<uint32_t>(kMaxBlocks, p.sc.spill_lanes / kBlock) : kMaxBlocks, st,
+            wide_lds_bytes(p.sc, false));
+      return;
+    case TF_STACK:
+      if constexpr (family_built(KF_STACK)) {
+        if (early)
+          launch_occl_k<R, StackTrav<R, kStackDepth>, true>(p, kMaxBlocks, st);
+        else
+          launch_occl_k<R, StackTrav<R, kStackDepth>, false>(p, kMaxBlocks, st);
+      }
+      return;
+  }
+}
+
 // The feature-buffer pass: the same instantiations (each in its base and its extended form), a lane per pixel
 template <class R>
 void launch_aov(const AovParams<R>& ap, TraceFamily fam, hipStream_t st) {
@@ -2198,6 +2327,7 @@ void launch_pixmap(const uint4* tiles, uint32_t ntiles, uint32_t npix, uint32_t*
   template void launch_init<R>(const LaunchParams<R>&, uint32_t, hipStream_t);                                   \
   template void launch_trace<R>(const TraceParams<R>&, TraceFamily, hipStream_t);                                \
   template void launch_aov<R>(const AovParams<R>&, TraceFamily, hipStream_t);                                    \
+  template void launch_occluded<R>(const OcclParams<R>&, TraceFamily, bool, hipStream_t);                        \
   template void launch_resolve<R>(const R*, uint32_t, uint32_t, uint32_t, R*, bool, bool, hipStream_t);
 RT_INSTANTIATE(double)
 RT_INSTANTIATE(float)

@@ -136,6 +136,23 @@ struct TraceParams {
 template <class R>
 void launch_trace(const TraceParams<R>& p, TraceFamily fam, hipStream_t st);
 
+// ---- occlusion queries (rt_occluded): the argument of k_occluded, rays as TraceParams'.
+//   out  [n] bytes  1: world.hit(r, interval(0.001, tmax)) is true, 0: it is not
+template <class R>
+struct OcclParams {
+  DevScene<R> sc;  // cam64 = nullptr, as a query's
+  const double* rays;
+  uint8_t* out;
+  uint32_t n;
+  uint64_t seed;
+  unsigned long long* seg_shards;  // [0] += n (rt_counters.segments)
+};
+// One occlusion launch of family `fam` (built as launch_trace's), the grid as launch_trace's. early: what
+// occlusion_early_exit (rt_plan.h) says of the scene: the any-hit kernel, else the closest-hit traversal with k_trace's
+// draws (only the linear program and the binary BVH have that second form; the others ignore `early`).
+template <class R>
+void launch_occluded(const OcclParams<R>& p, TraceFamily fam, bool early, hipStream_t st);
+
 // ---- feature buffers (rt_render_aov) and camera rays (rt_camera_rays). Their own kernargs, for the reason above.
 //   pixmap  local pixel -> x | y << 16 (launch_pixmap), camx the camera view (make_view) in device memory
 //   feat  [npix][8] doubles  albedo, normal, depth, hit: the means over the pixel's samples (four 16-byte stores)

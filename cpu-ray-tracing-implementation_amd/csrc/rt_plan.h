@@ -81,6 +81,23 @@ inline TraceFamily aov_family(const SceneHeader& h, bool ordered, size_t word_by
 inline bool aov_extended(const SceneHeader& h, int32_t cam_mode) {
   return cam_mode != RT_CAM_PERSPECTIVE || (h.tex_kinds & ~((1u << T_SOLID) | (1u << T_CHECKER))) != 0;
 }
+// Whether an occlusion query (rt_occluded) of family `f` may start its traversal bounded by the ray's tmax and leave
+// at the first accepted hit, or has to walk rt_trace_rays' closest-hit traversal and compare its t with tmax. The one
+// home of that decision ("Occlusion queries"). Two cases keep the closest-hit traversal:
+//  - a scene with volumes: volumne::hit draws with a running slot counter after its interval test, so another
+//    interval or an earlier exit shifts the later draws;
+//  - fp32 rays (word_bytes 16) through the binary BVH of a scene with the fp64 quad records (has_quads64): a near-edge
+//    quad hit is re-decided by a second, fp64 distance against the same interval (quad_edge64), so whether a quad
+//    accepts depends on the interval's upper end and not only on whether its root lies inside.
+// Both concern the linear program and the binary BVH alone: the flat program and the wide tree hold world-level
+// quads, spheres and triangles only (scene_compile.cpp), and neither re-decides a quad in fp64.
+// h: the header of the blob the rays read, as for trace_family.
+inline bool occlusion_early_exit(const SceneHeader& h, TraceFamily f, size_t word_bytes) {
+  if (f != TF_LINEAR && f != TF_STACK) return true;
+  if (h.has_volumes != 0) return false;
+  if (f == TF_STACK && word_bytes == 16 && h.has_quads64 != 0) return false;
+  return true;
+}
 // the render family whose RT_DEV_ONLY switch decides whether a build has the query kernel of `f`
 inline KernelFamily trace_render_family(TraceFamily f) {
   return f == TF_FLAT ? KF_FLAT : f == TF_LINEAR ? KF_LIN_ALL : f == TF_STACK ? KF_STACK : KF_WIDE;

@@ -605,6 +605,51 @@ rt_status trace_rays(rt_context* c, const rt_trace_params* prm, const double* ra
   return RT_OK;
 }
 
+// rt_occluded for one precision: trace_rays' family, stream and counters; one byte a ray (host path: in q_ids).
+template <class R>
+rt_status occluded(rt_context* c, const rt_trace_params* prm, const double* rays, uint32_t n, uint8_t* out,
+                   hipStream_t st) {
+  const bool f64 = sizeof(R) == 8;
+  const CompiledScene& cs = c->scene;
+  const SceneHeader& hdr = f64 ? cs.hdr64 : cs.hdr;
+  void* sbase = f64 ? c->scene64.ptr : c->scene32.ptr;
+  const bool ordered = prm->traversal == RT_TRAV_ORDERED;
+  const TraceFamily fam = trace_family(hdr, ordered, sizeof(typename WWord<R>::T));
+  if (!family_built(trace_render_family(fam)))
+    return set_err(c, RT_ERR_UNSUPPORTED,
+                   std::string("this build (RT_DEV_ONLY) has no ") + trace_family_name(fam) + " occlusion kernel");
+  rt_status s;
+  if ((s = query_scene(c, f64, st)) != RT_OK) return s;
+  OcclParams<R> p{};
+  p.rays = rays;
+  p.out = out;
+  if (!prm->on_device) {
+    if ((s = ensure(c, c->q_rays, 64ull * n)) != RT_OK) return s;
+    if ((s = ensure(c, c->q_ids, n)) != RT_OK) return s;
+    RT_HIP(c, hipMemcpyAsync(c->q_rays.ptr, rays, 64ull * n, hipMemcpyHostToDevice, st));
+    p.rays = (const double*)c->q_rays.ptr;
+    p.out = (uint8_t*)c->q_ids.ptr;
+  }
+  p.sc = dev_scene<R>(hdr, sbase);
+  if (fam == TF_WIDE_HBM && (s = wide_spill_area<R>(c, hdr, p.sc)) != RT_OK) return s;
+  if (ordered) p.sc.has_flat = p.sc.has_wide = 0;
+  p.sc.cam64 = nullptr;  // as trace_rays
+  p.n = n;
+  p.seed = prm->seed;
+  p.seg_shards = (unsigned long long*)c->counters.ptr;
+  launch_occluded<R>(p, fam, occlusion_early_exit(hdr, fam, sizeof(typename WWord<R>::T)), st);
+  RT_HIP(c, hipGetLastError());
+  c->last.launches++;
+  c->pending = true;  // as trace_rays
+  c->pend_stream = st;
+  if (!prm->on_device) {
+    RT_HIP(c, hipMemcpyAsync(out, p.out, n, hipMemcpyDeviceToHost, st));
+    RT_HIP(c, hipStreamSynchronize(st));
+    if ((s = settle(c)) != RT_OK) return s;
+  }
+  return RT_OK;
+}
+
 // rt_camera_rays: the rays of samples [first_sample, first_sample + spp) of the tiles' pixels, n = npix * spp rows.
 rt_status camera_rays(rt_context* c, const rt_camera_desc* cam, uint64_t seed, int32_t first_sample, uint32_t spp,
                       const std::vector<uint4>& tl, uint32_t npix, double* out, bool on_device, hipStream_t st) {
@@ -907,6 +952,30 @@ rt_status rt_trace_rays(rt_context* c, const rt_trace_params* prm, const double*
   try {
     if (prm->precision == RT_PREC_F64) return trace_rays<double>(c, prm, rays, (uint32_t)nrays, out_geom, out_ids, st);
     return trace_rays<float>(c, prm, rays, (uint32_t)nrays, out_geom, out_ids, st);
+  } catch (const std::bad_alloc&) {
+    return set_err(c, RT_ERR_OUT_OF_MEMORY, "out of host memory");
+  }
+}
+
+rt_status rt_occluded(rt_context* c, const rt_trace_params* prm, const double* rays, int64_t nrays,
+                      uint8_t* out_occluded, void* stream) {
+  if (!c) return set_err(nullptr, RT_ERR_INVALID_ARGUMENT, "null context");
+  if (!prm || !rays || !out_occluded) return set_err(c, RT_ERR_INVALID_ARGUMENT, "null argument");
+  if (nrays < 0 || nrays >= (1ll << 31)) return set_err(c, RT_ERR_INVALID_ARGUMENT, "nrays outside [0, 2^31)");
+  if (prm->precision != RT_PREC_F32 && prm->precision != RT_PREC_F64)
+    return set_err(c, RT_ERR_INVALID_ARGUMENT, "unknown precision");
+  if (prm->traversal != RT_TRAV_AUTO && prm->traversal != RT_TRAV_ORDERED)
+    return set_err(c, RT_ERR_INVALID_ARGUMENT, "unknown traversal");
+  if (prm->on_device && (uintptr_t)rays % 16 != 0)  // the kernel reads a ray as 16-byte words
+    return set_err(c, RT_ERR_INVALID_ARGUMENT, "device rays must be 16-byte aligned");
+  if (!c->has_scene) return set_err(c, RT_ERR_NO_SCENE, "rt_scene_upload has not succeeded on this context");
+  if (nrays == 0) return RT_OK;
+  RT_HIP(c, hipSetDevice(c->device));
+  // the stream as rt_trace_rays takes it
+  hipStream_t st = (stream == nullptr && !prm->on_device) ? c->stream : (hipStream_t)stream;
+  try {
+    if (prm->precision == RT_PREC_F64) return occluded<double>(c, prm, rays, (uint32_t)nrays, out_occluded, st);
+    return occluded<float>(c, prm, rays, (uint32_t)nrays, out_occluded, st);
   } catch (const std::bad_alloc&) {
     return set_err(c, RT_ERR_OUT_OF_MEMORY, "out of host memory");
   }

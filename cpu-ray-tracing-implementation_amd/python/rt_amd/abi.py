@@ -119,6 +119,8 @@ SIGNATURES = {
     "rt_trace_rays": (c_int32, [ctypes.c_void_p, ctypes.POINTER(rt_trace_params), ctypes.c_void_p, ctypes.c_int64,
                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "rt_trace_family": (c_int32, [ctypes.c_void_p, c_int32, c_int32]),
+    "rt_occluded": (c_int32, [ctypes.c_void_p, ctypes.POINTER(rt_trace_params), ctypes.c_void_p, ctypes.c_int64,
+                              ctypes.c_void_p, ctypes.c_void_p]),
     "rt_camera_rays": (c_int32, [ctypes.c_void_p, ctypes.POINTER(rt_camera_desc), c_uint64, c_int32, c_int32,
                                  ctypes.POINTER(rt_tile), c_int32, ctypes.c_void_p, c_int32, ctypes.c_void_p]),
     "rt_render_aov": (c_int32, [ctypes.c_void_p, ctypes.POINTER(rt_camera_desc), ctypes.POINTER(rt_aov_params),

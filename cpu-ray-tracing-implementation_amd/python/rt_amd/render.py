@@ -117,6 +117,47 @@ class Context:
                                            ctypes.c_void_p(self._stream_handle(stream))))
         return geom, ids
 
+    def occluded(self, rays, precision=abi.RT_PREC_F64, traversal=0, seed=1, stream=None, out=None):
+        """Whether anything lies on each ray within [0.001, tmax]: `rays` as trace_rays takes them -> (n,) uint8, 1
+        exactly where trace_rays with the same arguments reports a hit. An any-hit query with early exit
+        (rt_occluded): for a segment from p to q pass o = p, d = q - p and a tmax just below 1.
+
+        A C-contiguous numpy array takes the host path and returns a numpy array; a float64 torch tensor on the
+        context's device takes the device path, ordered on `stream` (default torch's current stream), and returns a
+        torch.uint8 tensor on that device -- the first n bytes of `out` where one is given (device path only: a
+        contiguous torch.uint8 tensor of at least n elements on that device; the call writes nothing past them)."""
+        prm = abi.rt_trace_params(seed=seed, precision=precision, traversal=traversal, on_device=0)
+        if isinstance(rays, np.ndarray):
+            if rays.dtype != np.float64 or rays.ndim != 2 or rays.shape[1] != 8 or not rays.flags.c_contiguous:
+                raise ValueError("rays: a C-contiguous (n, 8) float64 array")
+            if out is not None:
+                raise ValueError("out: only with the device path")
+            n = rays.shape[0]
+            out = np.empty((max(n, 1),), dtype=np.uint8)[:n]
+            pad = np.zeros(8)  # (an empty array still hands over valid pointers, as trace_rays)
+            self._check(self.lib.rt_occluded(self.h, ctypes.byref(prm), rays.ctypes.data if n else pad.ctypes.data, n,
+                                             out.ctypes.data if n else pad.ctypes.data,
+                                             ctypes.c_void_p(self._stream_handle(stream) if stream else 0)))
+            return out
+        import torch
+        if not (isinstance(rays, torch.Tensor) and rays.is_cuda and rays.dtype == torch.float64 and rays.dim() == 2 and
+                rays.shape[1] == 8 and rays.is_contiguous()):
+            raise ValueError("rays: a contiguous (n, 8) float64 numpy array or CUDA/HIP torch tensor")
+        n = rays.shape[0]
+        if out is None:
+            out = torch.empty((max(n, 1),), dtype=torch.uint8, device=rays.device)
+        elif not (isinstance(out, torch.Tensor) and out.device == rays.device and out.dtype == torch.uint8 and
+                  out.dim() == 1 and out.is_contiguous() and out.shape[0] >= max(n, 1)):
+            raise ValueError("out: a contiguous 1-D torch.uint8 tensor of at least n elements on the rays' device")
+        prm.on_device = 1
+        if stream is None:
+            stream = torch.cuda.current_stream(rays.device)
+        src = rays if n else torch.zeros((1, 8), dtype=torch.float64, device=rays.device)
+        # (the whole tensor's pointer: an empty slice has none, and the call checks its arguments even for n = 0)
+        self._check(self.lib.rt_occluded(self.h, ctypes.byref(prm), ctypes.c_void_p(src.data_ptr()), n,
+                                         ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(self._stream_handle(stream))))
+        return out[:n]
+
     def _tiles(self, cam, tiles):
         """(ctypes tile array, count, pixels, whether it is the whole image as one tile)."""
         full = tiles is None

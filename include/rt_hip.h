@@ -335,6 +335,34 @@ rt_status rt_trace_rays(rt_context* ctx, const rt_trace_params* params, const do
  * for an unknown precision or traversal. */
 int32_t rt_trace_family(rt_context* ctx, int32_t precision, int32_t traversal);
 
+/* ---- occlusion queries: is anything in the way? (shadow rays, ambient occlusion, line of sight) ----
+ *
+ * out_occluded[i] = 1 if world.hit(r_i, interval(0.001, tmax_i), rec) is true, else 0: an any-hit query with early
+ * exit, one byte a ray. rays: rt_trace_rays' format (nrays x 8 doubles, o[3], d[3] not normalised, time, tmax), so
+ * rt_camera_rays' output and existing ray buffers work unchanged; params: rt_trace_params as is. out_occluded needs
+ * no alignment, and bytes outside [0, nrays) are never written.
+ *
+ * Contract: for every ray, out_occluded[i] == 1 exactly when rt_trace_rays, called with the same context, params and
+ * ray, reports a hit (finite t) -- both precisions, every family, every traversal, no tolerance. rt_trace_family
+ * names the traversal taken. A NaN tmax or one below 0.001 gives 0; tmax = +inf asks "does this ray hit anything".
+ *
+ * The traversal starts with the interval [0.001, bound] instead of [0.001, inf) and a ray ends at the first
+ * primitive that accepts. bound is the largest value of the kernel's precision <= tmax: RT_PREC_F32 rounds tmax
+ * toward -inf (+inf stays +inf), so that for a float t, t <= bound is rt_trace_rays' (double)t <= tmax.
+ * Volume rule: volumne::hit draws its random numbers after its interval test, with a running slot counter, so a
+ * scene with volumes runs rt_trace_rays' closest-hit traversal unchanged (unbounded, no early exit, the same draws:
+ * ray i as path (seed, pixel = i, sample = 0)) and compares its t with tmax. RT_PREC_F32 rays through the binary
+ * BVH (RT_TRACE_STACK) of a scene with quads do the same, because that traversal re-decides near-edge quad hits with
+ * a second distance in fp64 against the interval's upper end.
+ *
+ * Errors and stream-ordering are rt_trace_rays': RT_ERR_INVALID_ARGUMENT for a null pointer, nrays < 0 or >= 2^31, an
+ * unknown precision or traversal, a device rays pointer (on_device = 1) not aligned to 16 bytes; RT_ERR_NO_SCENE;
+ * RT_ERR_UNSUPPORTED for a family a development build omits. nrays == 0 launches nothing. Adds nrays to
+ * rt_counters.segments and 1 to launches; with on_device = 1 the call joins the context's outstanding work exactly as
+ * a device-output render does. */
+rt_status rt_occluded(rt_context* ctx, const rt_trace_params* params, const double* rays, int64_t nrays,
+                      uint8_t* out_occluded, void* stream);
+
 /* ---- camera rays and feature buffers (AOVs): what a frame's pixels see first ----
  *
  * rt_camera_rays writes the rays camera::generate_ray (camera.h:244-293) draws for a render, in rt_trace_rays'
