@@ -210,4 +210,59 @@ inline ItemPlan plan_items(uint32_t spp, int32_t samples_per_item, bool flat, ui
   return pl;
 }
 
+// ------------------------------------------------------------------ the launch lanes (frame overlap)
+// A persistent launch ends with a tail: its last paths, up to max_depth dependent segments each, run on a chip
+// that is nearly empty (a frame costs its work plus ~0.5 ms whatever its size). The next launch
+// could fill those SIMDs, but on one stream it starts only after the tail and the resolve behind it. So the
+// persistent launches of device-output renders alternate between two internal streams, the lanes, and each
+// writes one of two sets of what a launch writes (the item partial sums, the dequeue heads): launch n + 1's blocks
+// become resident as launch n's retire. k_persist never waits for another kernel, so two resident launches cannot
+// deadlock. The resolves, and so everything the caller sees, stay on the caller's stream.
+//
+// The one home of the ordering: for the context's next persistent launch, which lane and buffer set it takes and
+// what it waits for (rt_render.hip turns the answer into events; tests/test_lane_plan.py).
+struct LaneQuery {
+  bool knob;             // RT_FRAME_OVERLAP (default on)
+  bool device_out;       // a device-output render: the call returns before the image is there
+  bool persist;          // the persistent schedule (the wavefront schedule syncs with the host between launches)
+  bool shared_scratch;   // the launch writes the context's wide spill area, which is indexed by lane alone
+  bool second_set;       // the second lane and buffer set exist (false: their allocation failed)
+  uint64_t n;            // launches that went through the lanes on this context so far
+  bool inputs_written;   // something the kernel reads (scene, camera view, pixel map) was queued on a caller's
+                         // stream after the last lane launch that waited for that stream
+  bool prev_overlapped;  // the context's last path launch went through the lanes
+  bool lane_stale[2];    // the lane has not waited for the inputs event since it was last recorded
+  bool pending;         // the context has work outstanding on `prev`
+  const void* caller;    // the stream of this call
+  const void* prev;      // the stream of the outstanding work
+};
+struct LanePlan {
+  bool overlap;       // false: the serial chain on the caller's stream (set 0), as before the lanes
+  int lane, set;      // lane 0 is the context's own stream; the sets alternate with the lanes
+  bool sync_prev;     // the host waits for `prev` (and the lanes behind it) first: the caller's stream changed
+  bool wait_resolve;  // the lane waits for the resolve of launch n - 2, the last reader of this set
+  bool record_inputs; // the inputs event is recorded now on the caller's stream (both lanes become stale)
+  bool wait_inputs;   // the lane waits for the inputs event as last recorded
+};
+inline LanePlan lane_plan(const LaneQuery& q) {
+  LanePlan pl{};
+  // a render on another stream than the outstanding work's: that work reads what this call is about to write
+  pl.sync_prev = q.pending && q.prev != q.caller;
+  pl.overlap = q.knob && q.device_out && q.persist && !q.shared_scratch && q.second_set;
+  if (!pl.overlap) return pl;
+  pl.lane = pl.set = (int)(q.n & 1);
+  // Launch n - 2 ran on this lane, so the kernels are in order already; its resolve ran on a caller's stream
+  // (after a host wait it has finished, and the wait for its event costs nothing).
+  pl.wait_resolve = q.n >= 2;
+  // Inputs queued on the caller's stream, or a serial launch there that wrote set 0: an event behind them. The
+  // launch that records it waits for it, and so does the other lane's next launch, which reads the same inputs
+  // and is ordered behind its own lane and the resolve of launch n - 1 alone, both older than the event.
+  // Inputs a caller queues *later* need nothing here: the caller's stream waits for every launch before that
+  // launch's resolve, so whatever follows on it is behind every earlier launch. A call that changes no input
+  // waits for nothing on the caller's stream but the resolve of launch n - 2: that is the case that overlaps.
+  pl.record_inputs = q.inputs_written || !q.prev_overlapped;
+  pl.wait_inputs = pl.record_inputs || q.lane_stale[pl.lane];
+  return pl;
+}
+
 }  // namespace rtd

@@ -62,6 +62,21 @@ struct rt_context {
   // query after rt_scene_upload on that query's stream; device copies of a host-pointer query's rays and outputs
   DevBuf ids, q_rays, q_geom, q_ids;
   bool ids_dirty = false;
+  // the launch lanes (rt_plan.h lane_plan): lane 0 is `stream`, lane 1 a second internal stream; launch n of the
+  // lanes runs on lane n & 1 and writes partial / heads (n even) or partial2 / heads2 (n odd). Made by the first
+  // render that overlaps; a context that never does holds none of it.
+  hipStream_t lane1 = nullptr;
+  DevBuf partial2, heads2;
+  hipEvent_t ev_done[2] = {nullptr, nullptr};     // launch on this lane finished (the caller's stream waits for it)
+  hipEvent_t ev_resolved[2] = {nullptr, nullptr}; // this set's resolve finished, on the caller's stream
+  hipEvent_t ev_inputs = nullptr;                 // the caller's stream, behind the inputs a call queued there
+  bool lanes_failed = false;     // making them failed once (out of memory): the context stays serial
+  uint64_t lane_launches = 0;    // launches that went through the lanes
+  bool lanes_live = false;       // a lane may still be running (cleared by wait_pending)
+  bool inputs_written = false;   // LaneQuery::inputs_written
+  bool prev_overlapped = false;  // LaneQuery::prev_overlapped
+  bool lane_stale[2] = {false, false};  // LaneQuery::lane_stale
+  std::vector<uint8_t> ev_lane;  // per pair of timing events: recorded on a lane (settle() clamps its start)
 };
 
 namespace {
@@ -116,13 +131,28 @@ rt_status set_err(rt_context* c, rt_status s, const std::string& m) {
       return set_err((ctx), RT_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
   } while (0)
 
+// Wait on the host for everything of this context that may still run. pend_stream alone covers the lanes in the
+// normal course (it waits for every lane launch before that launch's resolve); the lanes are waited for too, so
+// that a call which failed between a launch and that wait leaves nothing behind either. `pending` stays: the
+// device-side results are still to be folded in by settle().
+rt_status wait_pending(rt_context* c) {
+  if (c->pending) RT_HIP(c, hipStreamSynchronize(c->pend_stream));
+  if (c->lanes_live) {
+    RT_HIP(c, hipStreamSynchronize(c->stream));
+    if (c->lane1) RT_HIP(c, hipStreamSynchronize(c->lane1));
+    c->lanes_live = false;
+  }
+  return RT_OK;
+}
+
 // Grow a context buffer. The only work that can still read the old buffer is this context's
 // outstanding device-output render (host-output renders return finished, and a render on another
-// stream waits for pend_stream first): wait for that stream, not for the whole device.
+// stream waits for pend_stream first): wait for that stream and the lanes, not for the whole device.
 rt_status ensure(rt_context* c, DevBuf& b, size_t bytes) {
   if (b.ptr && b.bytes >= bytes) return RT_OK;
   if (b.ptr) {
-    if (c->pending) RT_HIP(c, hipStreamSynchronize(c->pend_stream));
+    rt_status w;
+    if ((w = wait_pending(c)) != RT_OK) return w;
     RT_HIP(c, hipFree(b.ptr));
     b.ptr = nullptr;
     b.bytes = 0;
@@ -152,8 +182,11 @@ hipEvent_t take_event(rt_context* c, size_t idx) {
 // the cumulative segment count, the kernel time of the timing events, the fault word.
 rt_status settle(rt_context* c) {
   if (!c->pending) return RT_OK;
+  {
+    rt_status w;
+    if ((w = wait_pending(c)) != RT_OK) return w;
+  }
   c->pending = false;
-  RT_HIP(c, hipStreamSynchronize(c->pend_stream));
   unsigned long long* shards = (unsigned long long*)(c->total_host + 16);
   RT_HIP(c, hipMemcpy(shards, c->counters.ptr, sizeof(unsigned long long) * kSegShards, hipMemcpyDeviceToHost));
   uint64_t segs = 0;
@@ -163,9 +196,20 @@ rt_status settle(rt_context* c) {
   for (size_t k = 0; k + 1 < c->ev_used; k += 2) {
     float a = 0;
     RT_HIP(c, hipEventElapsedTime(&a, c->events[k], c->events[k + 1]));
+    // A lane launch's start event fires when its lane reaches it, which with two lanes is while the launch before
+    // still fills the chip. Its time counts from the later of its own start and that launch's end, so step_ms never
+    // counts a moment twice: it stays below the wall time and in steady state is the frame period (rt_counters).
+    if (k >= 2 && k / 2 < c->ev_lane.size() && c->ev_lane[k / 2]) {
+      float lead = 0;  // own start -> previous end; positive: the previous launch was still running
+      if (hipEventElapsedTime(&lead, c->events[k], c->events[k - 1]) == hipSuccess && lead > 0)
+        a = std::max(0.0f, a - lead);
+      else
+        (void)hipGetLastError();
+    }
     ms += a;
   }
   c->ev_used = 0;
+  c->ev_lane.clear();
   c->last.step_ms += ms;
   uint32_t fault = 0;
   if (c->fault.ptr) RT_HIP(c, hipMemcpy(&fault, c->fault.ptr, 4, hipMemcpyDeviceToHost));
@@ -262,6 +306,13 @@ PlanKnobs env_knobs() {
   return k;
 }
 
+// RT_FRAME_OVERLAP=0: every launch on the caller's stream, the chain as it was before the lanes (for A/B runs and
+// for profiles that need one kernel at a time). Read per call, as the knobs above.
+bool env_frame_overlap() {
+  const char* v = std::getenv("RT_FRAME_OVERLAP");
+  return !(v && *v) || std::strtol(v, nullptr, 10) != 0;
+}
+
 // What launch_step needs besides the parameters
 struct StepKind {
   KernelFamily fam;
@@ -271,7 +322,8 @@ struct StepKind {
 
 // One launch_step, between two events when the context collects kernel times (settle() sums the pairs)
 template <class R>
-rt_status timed_step(rt_context* c, const LaunchParams<R>& p, const StepKind& k, uint32_t grid, hipStream_t st) {
+rt_status timed_step(rt_context* c, const LaunchParams<R>& p, const StepKind& k, uint32_t grid, hipStream_t st,
+                     bool on_lane = false) {
   hipEvent_t e0 = nullptr, e1 = nullptr;
   if (c->timing) {
     e0 = take_event(c, c->ev_used);
@@ -282,6 +334,8 @@ rt_status timed_step(rt_context* c, const LaunchParams<R>& p, const StepKind& k,
   launch_step<R>(p, k.fam, k.ll, k.nl, k.lli, k.stack, grid, st);
   if (c->timing) {
     RT_HIP(c, hipEventRecord(e1, st));
+    c->ev_lane.resize(c->ev_used / 2 + 1, 0);
+    c->ev_lane[c->ev_used / 2] = on_lane;
     c->ev_used += 2;
   }
   c->last.launches++;
@@ -292,10 +346,11 @@ rt_status timed_step(rt_context* c, const LaunchParams<R>& p, const StepKind& k,
 // The persistent schedule (the default): one launch of at most `grid` blocks renders the pass. A fault is
 // reported by the settle after the call (rt_stats, or a host-output render).
 template <class R>
-rt_status run_persistent(rt_context* c, const LaunchParams<R>& p, const StepKind& k, uint32_t grid, hipStream_t st) {
-  RT_HIP(c, hipMemsetAsync(c->heads.ptr, 0, 4ull * kHeads * kHeadStride, st));
+rt_status run_persistent(rt_context* c, const LaunchParams<R>& p, const StepKind& k, uint32_t grid, hipStream_t st,
+                         bool on_lane = false) {
+  RT_HIP(c, hipMemsetAsync(p.heads, 0, 4ull * kHeads * kHeadStride, st));
   rt_status s;
-  if ((s = timed_step(c, p, k, grid, st)) != RT_OK) return s;
+  if ((s = timed_step(c, p, k, grid, st, on_lane)) != RT_OK) return s;
   RT_HIP(c, hipGetLastError());
   c->last.grid_lanes = last_grid_lanes();
   return RT_OK;
@@ -370,6 +425,7 @@ rt_status pixel_map(rt_context* c, const std::vector<uint4>& tl, uint32_t npix, 
     c->tiles_dev = tl;  // the copy's source outlives this call
     c->pixmap_for = c->pixmap.ptr;
     c->pixmap_npix = npix;
+    c->inputs_written = true;  // (whoever queues it: a feature-buffer call's map is a later render's input too)
     RT_HIP(c, hipMemcpyAsync(c->tiles.ptr, c->tiles_dev.data(), sizeof(uint4) * tl.size(), hipMemcpyHostToDevice, st));
     launch_pixmap((const uint4*)c->tiles.ptr, (uint32_t)tl.size(), npix, (uint32_t*)c->pixmap.ptr, st);
   }
@@ -382,11 +438,34 @@ rt_status camera_view(rt_context* c, const rt_camera_desc* cam, hipStream_t st) 
   c->cam_host = make_view(cam);
   if ((s = ensure(c, c->camx, sizeof(CamDev))) != RT_OK) return s;
   if (!c->cam_valid || std::memcmp(&c->cam_dev, &c->cam_host, sizeof(CamDev)) != 0) {
+    c->inputs_written = true;
     RT_HIP(c, hipMemcpyAsync(c->camx.ptr, &c->cam_host, sizeof(CamDev), hipMemcpyHostToDevice, st));
     c->cam_dev = c->cam_host;
     c->cam_valid = true;
   }
   return RT_OK;
+}
+
+// The second lane and buffer set (rt_plan.h lane_plan), made by the first render that overlaps and grown with the
+// first set. False when something cannot be had (the second partial buffer doubles the largest allocation of a
+// render): the render then takes the serial order, with no error. A stream or an event that cannot be made is not
+// tried again; the buffer is, because a later, smaller render may fit.
+bool lanes_ready(rt_context* c, size_t partial_bytes) {
+  if (c->lanes_failed) return false;
+  if (!c->lane1) {
+    bool ok = hipStreamCreateWithFlags(&c->lane1, hipStreamNonBlocking) == hipSuccess;
+    for (hipEvent_t* e : {&c->ev_done[0], &c->ev_done[1], &c->ev_resolved[0], &c->ev_resolved[1], &c->ev_inputs})
+      ok = ok && hipEventCreateWithFlags(e, hipEventDisableTiming) == hipSuccess;
+    if (!ok) {
+      (void)hipGetLastError();
+      c->lanes_failed = true;  // (what was made goes with the context)
+      return false;
+    }
+  }
+  const std::string err = c->err;
+  const bool ok = ensure(c, c->heads2, 4ull * kHeads * kHeadStride) == RT_OK && ensure(c, c->partial2, partial_bytes) == RT_OK;
+  if (!ok) c->err = err;
+  return ok;
 }
 
 template <class R>
@@ -400,9 +479,19 @@ rt_status render(rt_context* c, const rt_camera_desc* cam, const rt_render_param
   auto t0 = std::chrono::steady_clock::now();
   // A device-output render still pending on another stream reads the context's shared buffers
   // (pixmap, tiles, camx, heads, partial): wait for it before this call writes any of them.
-  if (c->pending && c->pend_stream != st) RT_HIP(c, hipStreamSynchronize(c->pend_stream));
+  // (lane_plan's sync_prev depends on these three fields alone; the rest of the query is filled in below)
+  LaneQuery lq{};
+  lq.pending = c->pending;
+  lq.caller = (const void*)st;
+  lq.prev = (const void*)c->pend_stream;
+  if (lane_plan(lq).sync_prev) {
+    rt_status w;
+    if ((w = wait_pending(c)) != RT_OK) return w;
+    lq.pending = false;  // nothing is running any more: the launches below have no other stream to wait for
+  }
   if (dirty) {  // the scene uploaded since the last render of this precision, stream-ordered before its kernels
     const std::vector<unsigned char>& blob = f64 ? cs.blob64 : cs.blob32;
+    c->inputs_written = true;
     RT_HIP(c, hipMemcpyAsync(sbase, blob.data(), blob.size(), hipMemcpyHostToDevice, st));
     dirty = false;
     // outstanding from here on, whatever this call does next (an empty tile list or max_depth <= 0
@@ -504,13 +593,64 @@ rt_status render(rt_context* c, const rt_camera_desc* cam, const rt_render_param
       if ((s = ensure(c, c->heads, 4ull * kHeads * kHeadStride)) != RT_OK) return s;
       p.heads = (uint32_t*)c->heads.ptr;
     }
+    // the launch lanes (rt_plan.h lane_plan): asked per launch, so the passes of a call alternate too
+    lq.knob = env_frame_overlap();
+    lq.device_out = out_dev != 0;
+    lq.persist = persist;
+    lq.shared_scratch = p.sc.wide_spill != nullptr;
+    lq.second_set = true;  // asked first whether the call would overlap at all; then whether the set can be had
+    lq.second_set = lane_plan(lq).overlap && lanes_ready(c, plan.partial_bytes);
     for (uint32_t c0 = 0; c0 < plan.nchunks; c0 += plan.cpp) {  // the passes (one for every BASELINE config but C5)
       const uint32_t pc = std::min(plan.cpp, plan.nchunks - c0);
       p.chunk0 = c0;
       p.n_items = npix * pc;
-      s = persist ? run_persistent(c, p, kind, nblk_max, st) : run_wavefront(c, p, kind, nblk_max, st);
-      if (s != RT_OK) return s;
-      launch_resolve<R>((const R*)c->partial.ptr, npix, pc, spp, (R*)dout, c0 == 0, c0 + pc >= plan.nchunks, st);
+      lq.n = c->lane_launches;
+      lq.inputs_written = c->inputs_written;
+      lq.prev_overlapped = c->prev_overlapped;
+      lq.lane_stale[0] = c->lane_stale[0];
+      lq.lane_stale[1] = c->lane_stale[1];
+      const LanePlan lp = lane_plan(lq);
+      const R* partial = (const R*)c->partial.ptr;
+      if (lp.overlap) {
+        hipStream_t lane = lp.lane ? c->lane1 : c->stream;
+        if (lp.set) {
+          p.partial = (R*)c->partial2.ptr;
+          p.heads = (uint32_t*)c->heads2.ptr;
+        } else {
+          p.partial = (R*)c->partial.ptr;
+          p.heads = (uint32_t*)c->heads.ptr;
+        }
+        partial = p.partial;
+        // outstanding from here on, the lanes included, whatever fails below
+        c->pending = true;
+        c->pend_stream = st;
+        c->lanes_live = true;
+        if (lp.wait_resolve) RT_HIP(c, hipStreamWaitEvent(lane, c->ev_resolved[lp.set], 0));
+        if (lp.record_inputs) {
+          RT_HIP(c, hipEventRecord(c->ev_inputs, st));
+          c->inputs_written = false;
+          c->lane_stale[0] = c->lane_stale[1] = true;  // neither lane is behind this event yet
+        }
+        if (lp.wait_inputs) {
+          RT_HIP(c, hipStreamWaitEvent(lane, c->ev_inputs, 0));
+          c->lane_stale[lp.lane] = false;
+        }
+        c->prev_overlapped = true;
+        c->lane_launches++;
+        if ((s = run_persistent(c, p, kind, nblk_max, lane, true)) != RT_OK) return s;
+        RT_HIP(c, hipEventRecord(c->ev_done[lp.lane], lane));
+        // The caller's stream takes the launch in here, before its resolve: `out` is written on the caller's stream
+        // alone, in the order of the calls, and whatever the caller queues behind this call (the next call's uploads
+        // among it) is behind every launch so far.
+        RT_HIP(c, hipStreamWaitEvent(st, c->ev_done[lp.lane], 0));
+      } else {
+        c->prev_overlapped = false;
+        c->inputs_written = false;  // the launch runs on the stream the inputs were queued on
+        s = persist ? run_persistent(c, p, kind, nblk_max, st) : run_wavefront(c, p, kind, nblk_max, st);
+        if (s != RT_OK) return s;
+      }
+      launch_resolve<R>(partial, npix, pc, spp, (R*)dout, c0 == 0, c0 + pc >= plan.nchunks, st);
+      if (lp.overlap) RT_HIP(c, hipEventRecord(c->ev_resolved[lp.set], st));
       c->last.launches++;
       RT_HIP(c, hipGetLastError());
     }
@@ -536,9 +676,11 @@ rt_status render(rt_context* c, const rt_camera_desc* cam, const rt_render_param
 rt_status query_scene(rt_context* c, bool f64, hipStream_t st) {
   const CompiledScene& cs = c->scene;
   bool& dirty = f64 ? c->scene_dirty64 : c->scene_dirty32;
-  if (c->pending && c->pend_stream != st) RT_HIP(c, hipStreamSynchronize(c->pend_stream));
+  rt_status s0;
+  if (c->pending && c->pend_stream != st && (s0 = wait_pending(c)) != RT_OK) return s0;
   if (dirty) {
     const std::vector<unsigned char>& blob = f64 ? cs.blob64 : cs.blob32;
+    c->inputs_written = true;
     RT_HIP(c, hipMemcpyAsync(f64 ? c->scene64.ptr : c->scene32.ptr, blob.data(), blob.size(), hipMemcpyHostToDevice, st));
     dirty = false;
     c->pending = true;
@@ -655,7 +797,7 @@ rt_status camera_rays(rt_context* c, const rt_camera_desc* cam, uint64_t seed, i
                       const std::vector<uint4>& tl, uint32_t npix, double* out, bool on_device, hipStream_t st) {
   rt_status s;
   // as render: work of this context pending on another stream reads the pixel map and the camera view
-  if (c->pending && c->pend_stream != st) RT_HIP(c, hipStreamSynchronize(c->pend_stream));
+  if (c->pending && c->pend_stream != st && (s = wait_pending(c)) != RT_OK) return s;
   if ((s = pixel_map(c, tl, npix, st)) != RT_OK) return s;
   if ((s = camera_view(c, cam, st)) != RT_OK) return s;
   const uint64_t n = (uint64_t)npix * spp;
@@ -825,7 +967,11 @@ void rt_context_destroy(rt_context* c) {
   // dropped with the context: nobody is left to report it to)
   if (c->pending) (void)hipStreamSynchronize(c->pend_stream);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
-  for (DevBuf* b : {&c->scene32, &c->scene64, &c->state, &c->partial, &c->pixmap, &c->queue0, &c->queue1, &c->blk, &c->wide_spill,
+  if (c->lane1) (void)hipStreamSynchronize(c->lane1);
+  for (hipEvent_t e : {c->ev_done[0], c->ev_done[1], c->ev_resolved[0], c->ev_resolved[1], c->ev_inputs})
+    if (e) (void)hipEventDestroy(e);
+  if (c->lane1) (void)hipStreamDestroy(c->lane1);
+  for (DevBuf* b : {&c->partial2, &c->heads2, &c->scene32, &c->scene64, &c->state, &c->partial, &c->pixmap, &c->queue0, &c->queue1, &c->blk, &c->wide_spill,
                     &c->out_tmp, &c->counters, &c->camx, &c->heads, &c->tiles, &c->fault, &c->ids, &c->q_rays, &c->q_geom,
                     &c->q_ids})
     if (b->ptr) (void)hipFree(b->ptr);
@@ -848,8 +994,8 @@ rt_status rt_scene_upload(rt_context* c, const rt_scene_desc* desc) {
   std::string err;
   rt_status s = compile_scene(desc, &cs, &err);
   if (s != RT_OK) return set_err(c, s, err);
-  // renders still pending on any stream read the current scene buffers
-  if (c->pending) RT_HIP(c, hipStreamSynchronize(c->pend_stream));
+  // renders still pending on any stream, and on the lanes, read the current scene buffers
+  if ((s = wait_pending(c)) != RT_OK) return s;
   if ((s = ensure(c, c->scene32, cs.blob32.size())) != RT_OK) return s;
   if ((s = ensure(c, c->scene64, cs.blob64.size())) != RT_OK) return s;
   if ((s = ensure(c, c->ids, cs.ids.size() * sizeof(int32_t))) != RT_OK) return s;

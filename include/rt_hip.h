@@ -222,7 +222,11 @@ typedef struct rt_counters {
   uint64_t iterations; /* extend/shade rounds (k_persist launches, or k_step rounds) */
   uint64_t launches;   /* kernel launches */
   double last_render_ms; /* host time of the last rt_render_tiles call (enqueue time when asynchronous) */
-  double step_ms; /* device time of the path-step kernels (when timing is enabled) */
+  double step_ms; /* device time of the path-step kernels (when timing is enabled): the sum over launches of
+                     (end event - start event). Consecutive device-output renders overlap (two launches may be
+                     resident, INTEGRATION.md "Streams and ordering"); such a launch counts from the later of its
+                     own start event and the end event of the launch before it, so no moment is counted twice:
+                     step_ms <= wall time, and in steady state step_ms / iterations is the frame period */
   double aux_ms;  /* rt_multi_stats: device time of the gather + unpack; otherwise 0 */
   uint64_t grid_lanes; /* lanes of the last persistent-kernel launch: the resident grid the occupancy
                           query gave that kernel on this device */
