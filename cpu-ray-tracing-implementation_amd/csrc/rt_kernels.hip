@@ -904,9 +904,13 @@ struct TravDefaults {
   // the segment loop tests the segment cap between trace and shade, as every kernel did before round 9, instead of
   // after shade (persist_body)
   static constexpr bool kCapBeforeShade = false;
+  // occlusion queries: the policy also has k_occluded's closest-hit form (EARLY = false), which launch_occluded takes
+  // where occlusion_early_exit (rt_plan.h) refuses the any-hit form. A policy without it always takes the any-hit form.
+  [[maybe_unused]] static constexpr bool kClosestOccl = false;
 };
 template <class R, bool SPH, bool TRI, bool VOL, bool LLI = false>
 struct LinearTrav : TravDefaults {
+  static constexpr bool kClosestOccl = true;  // (volumes draw after their interval test: occlusion_early_exit)
   static constexpr bool kLL = LLI, kLLI = LLI;
   // waves per SIMD the register budget is cut for (occupancy hides the shading loads); the
   // lean quad-only program fits 96 VGPRs with a small spill, the others would spill heavily
@@ -999,6 +1003,7 @@ struct FlatTrav : TravDefaults {
 constexpr uint32_t kLdsNodeMax = 256;
 template <class R, int STACK, bool LDSN = false>
 struct StackTrav : TravDefaults {  // (no cold state in LDS: its LDS holds the traversal stacks)
+  static constexpr bool kClosestOccl = true;  // (fp32 rays re-decide near-edge quad hits in fp64: occlusion_early_exit)
   static constexpr int kStack = STACK;
   static constexpr int kLdsNodes = LDSN ? (int)kLdsNodeMax : 0;
   static constexpr int kWaves = sizeof(R) == 4 ? RT_STACK_WAVES : (LDSN ? 1 : RT_STACK_WAVES_F64);  // occupancy over a small spill
@@ -2106,20 +2111,41 @@ void launch_resident(KernelT kern, const P& p, uint32_t n, uint32_t max_blocks, 
   if (res > 0) grid = std::min(grid, res);
   hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), lds, st, p);
 }
-template <class R, class Trav>
-void launch_trace_k(const KTrace<R>& p, uint32_t max_blocks, hipStream_t st, size_t lds = 0) {
-  launch_resident(k_trace<R, Trav>, p, p.n, max_blocks, st, lds);
-}
-template <class R, class Trav, bool EARLY>
-void launch_occl_k(const KOccl<R>& p, uint32_t max_blocks, hipStream_t st, size_t lds = 0) {
-  launch_resident(k_occluded<R, Trav, EARLY>, p, p.n, max_blocks, st, lds);
-}
-template <class R, class Trav>
-void launch_aov_k(const KAov<R>& p, uint32_t max_blocks, hipStream_t st, size_t lds = 0) {
-  if (p.ext)
-    launch_resident(k_aov<R, Trav, true>, p, p.npix, max_blocks, st, lds);
-  else
-    launch_resident(k_aov<R, Trav, false>, p, p.npix, max_blocks, st, lds);
+
+// The traversal of a query family: one instantiation per family and precision, the most general one -- every primitive
+// kind (the linear program's volumes too), the deepest binary-BVH stack with its nodes in HBM, the flat program's
+// records in global memory. The one list of them: launch_trace, launch_occluded and launch_aov name only their kernel.
+// Calls f(TravTag of the family's policy, the most blocks a launch may have, its dynamic LDS bytes) if this build has
+// the family (family_built), and nothing otherwise.
+template <class Trav>
+struct TravTag {
+  using type = Trav;
+};
+template <class R, class F>
+void with_query_family(const DevScene<R>& sc, TraceFamily fam, F&& f) {
+  constexpr uint32_t kMaxBlocks = 1u << 14;  // (the resident grid is below it on every device so far)
+  constexpr size_t kNoLds = 0;
+  switch (fam) {
+    case TF_FLAT:
+      if constexpr (family_built(KF_FLAT)) f(TravTag<FlatTrav<R>>{}, kMaxBlocks, kNoLds);
+      return;
+    case TF_LINEAR:
+      if constexpr (family_built(KF_LIN_ALL)) f(TravTag<LinearTrav<R, true, true, true>>{}, kMaxBlocks, kNoLds);
+      return;
+    case TF_WIDE_LDS:
+      if constexpr (family_built(KF_WIDE))
+        f(TravTag<WideTrav<R, true, true, true, true, true>>{}, kMaxBlocks, wide_lds_bytes(sc, true));
+      return;
+    case TF_WIDE_HBM:
+      if constexpr (family_built(KF_WIDE))  // the spill area holds spill_lanes lanes: never launch more
+        f(TravTag<WideTrav<R, true, true, true, true, false>>{},
+          sc.wide_spill ? std::min<uint32_t>(kMaxBlocks, sc.spill_lanes / kBlock) : kMaxBlocks,
+          wide_lds_bytes(sc, false));
+      return;
+    case TF_STACK:
+      if constexpr (family_built(KF_STACK)) f(TravTag<StackTrav<R, kStackDepth>>{}, kMaxBlocks, kNoLds);
+      return;
+  }
 }
 
 }  // namespace
@@ -2188,101 +2214,40 @@ void launch_step(const LaunchParams<R>& lp, KernelFamily fam, bool ll, bool nl, 
 
 uint64_t last_grid_lanes() { return t_grid_lanes; }
 
-// One instantiation per family and precision, the most general one: every primitive kind (the linear program's
-// volumes too), the deepest binary-BVH stack with its nodes in HBM, the flat program's records in global memory.
+// The three query launches: with_query_family's traversal of `fam`, each in its own kernel.
 template <class R>
 void launch_trace(const TraceParams<R>& tp, TraceFamily fam, hipStream_t st) {
   const KTrace<R> p{tp};
-  constexpr uint32_t kMaxBlocks = 1u << 14;  // (the resident grid is below it on every device so far)
-  switch (fam) {
-    case TF_FLAT:
-      if constexpr (family_built(KF_FLAT)) launch_trace_k<R, FlatTrav<R>>(p, kMaxBlocks, st);
-      return;
-    case TF_LINEAR:
-      if constexpr (family_built(KF_LIN_ALL)) launch_trace_k<R, LinearTrav<R, true, true, true>>(p, kMaxBlocks, st);
-      return;
-    case TF_WIDE_LDS:
-      if constexpr (family_built(KF_WIDE))
-        launch_trace_k<R, WideTrav<R, true, true, true, true, true>>(p, kMaxBlocks, st, wide_lds_bytes(p.sc, true));
-      return;
-    case TF_WIDE_HBM:
-      if constexpr (family_built(KF_WIDE))  // the spill area holds spill_lanes lanes: never launch more
-        launch_trace_k<R, WideTrav<R, true, true, true, true, false>>(
-            p, p.sc.wide_spill ? std::min<uint32_t>(kMaxBlocks, p.sc.spill_lanes / kBlock) : kMaxBlocks, st,
-            wide_lds_bytes(p.sc, false));
-      return;
-    case TF_STACK:
-      if constexpr (family_built(KF_STACK)) launch_trace_k<R, StackTrav<R, kStackDepth>>(p, kMaxBlocks, st);
-      return;
-  }
+  with_query_family(p.sc, fam, [&](auto trav, uint32_t max_blocks, size_t lds) {
+    launch_resident(k_trace<R, typename decltype(trav)::type>, p, p.n, max_blocks, st, lds);
+  });
 }
 
-// Occlusion queries: launch_trace's instantiations in their any-hit form, and the closest-hit form of the two
-// families occlusion_early_exit can refuse (the linear program and the binary BVH)
+// Occlusion queries: the any-hit form, or the closest-hit form of the families occlusion_early_exit can refuse
+// (Trav::kClosestOccl: decided per policy at compile time, so the others have no such kernel)
 template <class R>
 void launch_occluded(const OcclParams<R>& op, TraceFamily fam, bool early, hipStream_t st) {
   const KOccl<R> p{op};
-  constexpr uint32_t kMaxBlocks = 1u << 14;
-  switch (fam) {
-    case TF_FLAT:
-      if constexpr (family_built(KF_FLAT)) launch_occl_k<R, FlatTrav<R>, true>(p, kMaxBlocks, st);
-      return;
-    case TF_LINEAR:
-      if constexpr (family_built(KF_LIN_ALL)) {
-        if (early)
-          launch_occl_k<R, LinearTrav<R, true, true, true>, true>(p, kMaxBlocks, st);
-        else
-          launch_occl_k<R, LinearTrav<R, true, true, true>, false>(p, kMaxBlocks, st);
-      }
-      return;
-    case TF_WIDE_LDS:
-      if constexpr (family_built(KF_WIDE))
-        launch_occl_k<R, WideTrav<R, true, true, true, true, true>, true>(p, kMaxBlocks, st,
-                                                                          wide_lds_bytes(p.sc, true));
-      return;
-    case TF_WIDE_HBM:
-      if constexpr (family_built(KF_WIDE))  // the spill area holds spill_lanes lanes: never launch more
-        launch_occl_k<R, WideTrav<R, true, true, true, true, false>, true>(
-            p, p.sc.wide_spill ? std::min<uint32_t>(kMaxBlocks, p.sc.spill_lanes / kBlock) : kMaxBlocks, st,
-            wide_lds_bytes(p.sc, false));
-      return;
-    case TF_STACK:
-      if constexpr (family_built(KF_STACK)) {
-        if (early)
-          launch_occl_k<R, StackTrav<R, kStackDepth>, true>(p, kMaxBlocks, st);
-        else
-          launch_occl_k<R, StackTrav<R, kStackDepth>, false>(p, kMaxBlocks, st);
-      }
-      return;
-  }
+  with_query_family(p.sc, fam, [&](auto trav, uint32_t max_blocks, size_t lds) {
+    using Trav = typename decltype(trav)::type;
+    if (early || !Trav::kClosestOccl)
+      launch_resident(k_occluded<R, Trav, true>, p, p.n, max_blocks, st, lds);
+    else if constexpr (Trav::kClosestOccl)
+      launch_resident(k_occluded<R, Trav, false>, p, p.n, max_blocks, st, lds);
+  });
 }
 
-// The feature-buffer pass: the same instantiations (each in its base and its extended form), a lane per pixel
+// The feature-buffer pass: a lane per pixel, each traversal in its base and its extended form (rt_plan.h aov_extended)
 template <class R>
 void launch_aov(const AovParams<R>& ap, TraceFamily fam, hipStream_t st) {
   const KAov<R> p{ap};
-  constexpr uint32_t kMaxBlocks = 1u << 14;
-  switch (fam) {
-    case TF_FLAT:
-      if constexpr (family_built(KF_FLAT)) launch_aov_k<R, FlatTrav<R>>(p, kMaxBlocks, st);
-      return;
-    case TF_LINEAR:
-      if constexpr (family_built(KF_LIN_ALL)) launch_aov_k<R, LinearTrav<R, true, true, true>>(p, kMaxBlocks, st);
-      return;
-    case TF_WIDE_LDS:
-      if constexpr (family_built(KF_WIDE))
-        launch_aov_k<R, WideTrav<R, true, true, true, true, true>>(p, kMaxBlocks, st, wide_lds_bytes(p.sc, true));
-      return;
-    case TF_WIDE_HBM:
-      if constexpr (family_built(KF_WIDE))  // the spill area holds spill_lanes lanes: never launch more
-        launch_aov_k<R, WideTrav<R, true, true, true, true, false>>(
-            p, p.sc.wide_spill ? std::min<uint32_t>(kMaxBlocks, p.sc.spill_lanes / kBlock) : kMaxBlocks, st,
-            wide_lds_bytes(p.sc, false));
-      return;
-    case TF_STACK:
-      if constexpr (family_built(KF_STACK)) launch_aov_k<R, StackTrav<R, kStackDepth>>(p, kMaxBlocks, st);
-      return;
-  }
+  with_query_family(p.sc, fam, [&](auto trav, uint32_t max_blocks, size_t lds) {
+    using Trav = typename decltype(trav)::type;
+    if (p.ext)
+      launch_resident(k_aov<R, Trav, true>, p, p.npix, max_blocks, st, lds);
+    else
+      launch_resident(k_aov<R, Trav, false>, p, p.npix, max_blocks, st, lds);
+  });
 }
 void launch_camera_rays(const CamRayParams& p, hipStream_t st) {
   const uint32_t n = p.npix * p.spp;

@@ -132,7 +132,9 @@ struct TraceParams {
   unsigned long long* seg_shards;  // [0] += n (rt_counters.segments)
 };
 // One query launch of family `fam` (built: family_built(trace_render_family(fam))); the grid is what the chip
-// holds resident at most (and what the wide spill area holds), the lanes stride over the rays.
+// holds resident at most (and what the wide spill area holds), the lanes stride over the rays. The traversal of each
+// family, the block cap and the LDS bytes of this launch, launch_occluded and launch_aov are listed once, in
+// with_query_family (rt_kernels.hip).
 template <class R>
 void launch_trace(const TraceParams<R>& p, TraceFamily fam, hipStream_t st);
 
@@ -147,9 +149,10 @@ struct OcclParams {
   uint64_t seed;
   unsigned long long* seg_shards;  // [0] += n (rt_counters.segments)
 };
-// One occlusion launch of family `fam` (built as launch_trace's), the grid as launch_trace's. early: what
-// occlusion_early_exit (rt_plan.h) says of the scene: the any-hit kernel, else the closest-hit traversal with k_trace's
-// draws (only the linear program and the binary BVH have that second form; the others ignore `early`).
+// One occlusion launch of family `fam`: with_query_family's traversal, block cap and LDS bytes, as launch_trace. early:
+// what occlusion_early_exit (rt_plan.h) says of the scene: the any-hit kernel, else the closest-hit traversal with
+// k_trace's draws (only the policies with kClosestOccl, the linear program and the binary BVH, have that second form;
+// the others ignore `early`).
 template <class R>
 void launch_occluded(const OcclParams<R>& p, TraceFamily fam, bool early, hipStream_t st);
 
@@ -173,7 +176,8 @@ struct AovParams {
   unsigned long long* seg_shards;  // [0] += npix * spp
 };
 // One feature-buffer launch of family `fam` (aov_family; built: family_built(trace_render_family(fam))): a lane per
-// pixel, striding over the pixels when the chip (or the wide spill area) holds fewer lanes.
+// pixel, striding over the pixels when the chip (or the wide spill area) holds fewer lanes. with_query_family's
+// traversal, block cap and LDS bytes, as launch_trace; p.ext chooses between the kernel's two forms.
 template <class R>
 void launch_aov(const AovParams<R>& p, TraceFamily fam, hipStream_t st);
 

@@ -1,5 +1,6 @@
 // rt_render.hip -- the host side of librt_hip.so: contexts and their device buffers, render<R>() and its two
-// schedules, trace_rays<R>() (ray queries), camera_rays() and render_aov<R>() (feature buffers), and the C ABI of include/rt_hip.h. It contains no kernel: what a render launches goes through
+// schedules, the query path (trace_rays<R>(), occluded<R>(), camera_rays(), render_aov<R>()), and the C ABI of
+// include/rt_hip.h with its argument checks. It contains no kernel: what a render launches goes through
 // rt_launch.h (rt_kernels.hip), and its item layout and kernel family come from rt_plan.h.
 #include <hip/hip_runtime.h>
 
@@ -468,6 +469,43 @@ bool lanes_ready(rt_context* c, size_t partial_bytes) {
   return ok;
 }
 
+// Work of this context still pending on another stream than `st` reads the context's shared buffers (pixmap, tiles,
+// camx, heads, partial, the scene): every call waits for it here before it writes any of them. lq: the three fields of
+// the lane query that lane_plan's sync_prev depends on, as they stand for the launches of this call.
+rt_status wait_other_stream(rt_context* c, hipStream_t st, LaneQuery* lq = nullptr) {
+  LaneQuery q{};
+  q.pending = c->pending;
+  q.caller = (const void*)st;
+  q.prev = (const void*)c->pend_stream;
+  if (lane_plan(q).sync_prev) {
+    rt_status w;
+    if ((w = wait_pending(c)) != RT_OK) return w;
+    q.pending = false;  // nothing is running any more: the launches below have no other stream to wait for
+  }
+  if (lq) *lq = q;
+  return RT_OK;
+}
+
+// The opening of every call that reads the scene: wait_other_stream, then the scene blob of the precision copied on
+// `st` if rt_scene_upload has replaced it since the last call of that precision, stream-ordered before the kernels.
+rt_status scene_to_device(rt_context* c, bool f64, hipStream_t st, LaneQuery* lq = nullptr) {
+  rt_status s;
+  if ((s = wait_other_stream(c, st, lq)) != RT_OK) return s;
+  bool& dirty = f64 ? c->scene_dirty64 : c->scene_dirty32;
+  if (dirty) {
+    const std::vector<unsigned char>& blob = f64 ? c->scene.blob64 : c->scene.blob32;
+    void* sbase = f64 ? c->scene64.ptr : c->scene32.ptr;
+    c->inputs_written = true;
+    RT_HIP(c, hipMemcpyAsync(sbase, blob.data(), blob.size(), hipMemcpyHostToDevice, st));
+    dirty = false;
+    // outstanding from here on, whatever the call does next (an empty tile list or max_depth <= 0
+    // launches nothing that reads the scene): a later call on another stream waits for st
+    c->pending = true;
+    c->pend_stream = st;
+  }
+  return RT_OK;
+}
+
 template <class R>
 rt_status render(rt_context* c, const rt_camera_desc* cam, const rt_render_params* prm, const rt_tile* tiles,
                  int32_t ntiles, void* out, int32_t out_dev, hipStream_t st) {
@@ -475,30 +513,10 @@ rt_status render(rt_context* c, const rt_camera_desc* cam, const rt_render_param
   const CompiledScene& cs = c->scene;
   const SceneHeader& hdr = f64 ? cs.hdr64 : cs.hdr;
   void* sbase = f64 ? c->scene64.ptr : c->scene32.ptr;
-  bool& dirty = f64 ? c->scene_dirty64 : c->scene_dirty32;
   auto t0 = std::chrono::steady_clock::now();
-  // A device-output render still pending on another stream reads the context's shared buffers
-  // (pixmap, tiles, camx, heads, partial): wait for it before this call writes any of them.
-  // (lane_plan's sync_prev depends on these three fields alone; the rest of the query is filled in below)
-  LaneQuery lq{};
-  lq.pending = c->pending;
-  lq.caller = (const void*)st;
-  lq.prev = (const void*)c->pend_stream;
-  if (lane_plan(lq).sync_prev) {
-    rt_status w;
-    if ((w = wait_pending(c)) != RT_OK) return w;
-    lq.pending = false;  // nothing is running any more: the launches below have no other stream to wait for
-  }
-  if (dirty) {  // the scene uploaded since the last render of this precision, stream-ordered before its kernels
-    const std::vector<unsigned char>& blob = f64 ? cs.blob64 : cs.blob32;
-    c->inputs_written = true;
-    RT_HIP(c, hipMemcpyAsync(sbase, blob.data(), blob.size(), hipMemcpyHostToDevice, st));
-    dirty = false;
-    // outstanding from here on, whatever this call does next (an empty tile list or max_depth <= 0
-    // launches nothing that reads the scene): a later render on another stream waits for st
-    c->pending = true;
-    c->pend_stream = st;
-  }
+  rt_status s;
+  LaneQuery lq{};  // (the rest of the query is filled in below)
+  if ((s = scene_to_device(c, f64, st, &lq)) != RT_OK) return s;
 
   // pixel map: tiles packed in order, row-major inside each tile (expanded by k_pixmap)
   uint64_t npix64 = 0;
@@ -507,7 +525,6 @@ rt_status render(rt_context* c, const rt_camera_desc* cam, const rt_render_param
   const uint32_t npix = (uint32_t)npix64;
   if (npix == 0) return RT_OK;
   const size_t out_elems = 3ull * npix;
-  rt_status s;
   void* dout = out;
   if (!out_dev) {
     if ((s = ensure(c, c->out_tmp, out_elems * sizeof(R))) != RT_OK) return s;
@@ -669,23 +686,25 @@ rt_status render(rt_context* c, const rt_camera_desc* cam, const rt_render_param
   return RT_OK;
 }
 
-// What a query or feature-buffer launch on `st` reads of the scene, in place: work of this context pending on another
-// stream is waited for (it reads the buffers written here and by the caller), then the scene blob of the precision
-// and the (object, material) tables are copied if rt_scene_upload has replaced them since, stream-ordered before
-// the kernel (a buffer of their own for the tables: the blobs stay the render kernels').
+// ---------------------------------------------------------------- the query path
+// What rt_trace_rays, rt_occluded, rt_render_aov and (the staging and the end alone) rt_camera_rays share. Each call:
+// query_kernel_built, query_scene, its staging on the host path (stage), query_dev_scene with its own flag rule, its
+// kernel arguments and launch, query_done.
+
+// A build without the kernel of family `fam` refuses the call; what: "query", "occlusion" or "feature-buffer"
+rt_status query_kernel_built(rt_context* c, TraceFamily fam, const char* what) {
+  if (family_built(trace_render_family(fam))) return RT_OK;
+  return set_err(c, RT_ERR_UNSUPPORTED,
+                 std::string("this build (RT_DEV_ONLY) has no ") + trace_family_name(fam) + " " + what + " kernel");
+}
+
+// What a query or feature-buffer launch on `st` reads of the scene, in place: scene_to_device, then the (object,
+// material) tables copied if rt_scene_upload has replaced them since (a buffer of their own: the blobs stay the render
+// kernels').
 rt_status query_scene(rt_context* c, bool f64, hipStream_t st) {
   const CompiledScene& cs = c->scene;
-  bool& dirty = f64 ? c->scene_dirty64 : c->scene_dirty32;
-  rt_status s0;
-  if (c->pending && c->pend_stream != st && (s0 = wait_pending(c)) != RT_OK) return s0;
-  if (dirty) {
-    const std::vector<unsigned char>& blob = f64 ? cs.blob64 : cs.blob32;
-    c->inputs_written = true;
-    RT_HIP(c, hipMemcpyAsync(f64 ? c->scene64.ptr : c->scene32.ptr, blob.data(), blob.size(), hipMemcpyHostToDevice, st));
-    dirty = false;
-    c->pending = true;
-    c->pend_stream = st;
-  }
+  rt_status s;
+  if ((s = scene_to_device(c, f64, st)) != RT_OK) return s;
   if (c->ids_dirty) {
     if (!cs.ids.empty())
       RT_HIP(c, hipMemcpyAsync(c->ids.ptr, cs.ids.data(), cs.ids.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
@@ -696,55 +715,80 @@ rt_status query_scene(rt_context* c, bool f64, hipStream_t st) {
   return RT_OK;
 }
 
+// The device scene of a launch of family `fam`, with the spill area of a deep wide tree. The caller clears has_flat and
+// has_wide by its own rule.
+template <class R>
+rt_status query_dev_scene(rt_context* c, TraceFamily fam, DevScene<R>& sc) {
+  const bool f64 = sizeof(R) == 8;
+  const SceneHeader& hdr = f64 ? c->scene.hdr64 : c->scene.hdr;
+  sc = dev_scene<R>(hdr, f64 ? c->scene64.ptr : c->scene32.ptr);
+  rt_status s;
+  if (fam == TF_WIDE_HBM && (s = wide_spill_area<R>(c, hdr, sc)) != RT_OK) return s;
+  // no camera: a near-edge quad hit is re-decided on the given ray, or the lane's own camera ray (quad_edge64)
+  sc.cam64 = nullptr;
+  return RT_OK;
+}
+
+// Host path: the context buffer `b`, grown to `bytes`, stands in for the caller's array behind `p`
+template <class T>
+rt_status stage(rt_context* c, DevBuf& b, size_t bytes, T*& p) {
+  rt_status s;
+  if ((s = ensure(c, b, bytes)) != RT_OK) return s;
+  p = (T*)b.ptr;
+  return RT_OK;
+}
+
+// The end of a call after its launch on `st`. The context has work outstanding on st (the launch reads the context's
+// buffers, and the segment counter on the device settles with rt_stats, as after a device-output render). Host path:
+// the staged outputs are copied out and the call returns finished and settled. counted: the launch is one of
+// rt_counters.launches (rt_camera_rays' is not).
+struct HostOut {
+  void* host;
+  const void* dev;
+  size_t bytes;
+};
+rt_status query_done(rt_context* c, hipStream_t st, bool counted, bool on_device, std::initializer_list<HostOut> outs) {
+  RT_HIP(c, hipGetLastError());
+  if (counted) c->last.launches++;
+  c->pending = true;
+  c->pend_stream = st;
+  if (on_device) return RT_OK;
+  for (const HostOut& o : outs) RT_HIP(c, hipMemcpyAsync(o.host, o.dev, o.bytes, hipMemcpyDeviceToHost, st));
+  RT_HIP(c, hipStreamSynchronize(st));
+  return settle(c);
+}
+
 // rt_trace_rays for one precision: n rays (0 < n < 2^31) through the family trace_family gives the scene.
 template <class R>
 rt_status trace_rays(rt_context* c, const rt_trace_params* prm, const double* rays, uint32_t n, double* geom,
                      int32_t* ids, hipStream_t st) {
   const bool f64 = sizeof(R) == 8;
   const CompiledScene& cs = c->scene;
-  const SceneHeader& hdr = f64 ? cs.hdr64 : cs.hdr;
-  void* sbase = f64 ? c->scene64.ptr : c->scene32.ptr;
   const bool ordered = prm->traversal == RT_TRAV_ORDERED;
-  const TraceFamily fam = trace_family(hdr, ordered, sizeof(typename WWord<R>::T));
-  if (!family_built(trace_render_family(fam)))
-    return set_err(c, RT_ERR_UNSUPPORTED,
-                   std::string("this build (RT_DEV_ONLY) has no ") + trace_family_name(fam) + " query kernel");
+  const TraceFamily fam = trace_family(f64 ? cs.hdr64 : cs.hdr, ordered, sizeof(typename WWord<R>::T));
   rt_status s;
+  if ((s = query_kernel_built(c, fam, "query")) != RT_OK) return s;
   if ((s = query_scene(c, f64, st)) != RT_OK) return s;
   TraceParams<R> p{};
   p.rays = rays;
   p.geom = geom;
   p.ids = ids;
   if (!prm->on_device) {
-    if ((s = ensure(c, c->q_rays, 64ull * n)) != RT_OK) return s;
-    if ((s = ensure(c, c->q_geom, 56ull * n)) != RT_OK) return s;
-    if ((s = ensure(c, c->q_ids, 16ull * n)) != RT_OK) return s;
+    if ((s = stage(c, c->q_rays, 64ull * n, p.rays)) != RT_OK) return s;
+    if ((s = stage(c, c->q_geom, 56ull * n, p.geom)) != RT_OK) return s;
+    if ((s = stage(c, c->q_ids, 16ull * n, p.ids)) != RT_OK) return s;
     RT_HIP(c, hipMemcpyAsync(c->q_rays.ptr, rays, 64ull * n, hipMemcpyHostToDevice, st));
-    p.rays = (const double*)c->q_rays.ptr;
-    p.geom = (double*)c->q_geom.ptr;
-    p.ids = (int32_t*)c->q_ids.ptr;
   }
-  p.sc = dev_scene<R>(hdr, sbase);
-  if (fam == TF_WIDE_HBM && (s = wide_spill_area<R>(c, hdr, p.sc)) != RT_OK) return s;
+  if ((s = query_dev_scene<R>(c, fam, p.sc)) != RT_OK) return s;
+  // a query leaves the flat program and the wide tree only when asked to (trace_family), so `ordered` says it all
   if (ordered) p.sc.has_flat = p.sc.has_wide = 0;
-  p.sc.cam64 = nullptr;  // no camera: a near-edge quad hit is re-decided on the given ray (quad_edge64)
   p.idtab = (const int2*)c->ids.ptr;
   for (int k = 0; k < 4; k++) p.id_off[k] = cs.ids_off[k];
   p.n = n;
   p.seed = prm->seed;
   p.seg_shards = (unsigned long long*)c->counters.ptr;
   launch_trace<R>(p, fam, st);
-  RT_HIP(c, hipGetLastError());
-  c->last.launches++;
-  c->pending = true;  // the segment counter (on the device) settles with rt_stats, as after a device-output render
-  c->pend_stream = st;
-  if (!prm->on_device) {
-    RT_HIP(c, hipMemcpyAsync(geom, p.geom, 56ull * n, hipMemcpyDeviceToHost, st));
-    RT_HIP(c, hipMemcpyAsync(ids, p.ids, 16ull * n, hipMemcpyDeviceToHost, st));
-    RT_HIP(c, hipStreamSynchronize(st));
-    if ((s = settle(c)) != RT_OK) return s;
-  }
-  return RT_OK;
+  return query_done(c, st, true, prm->on_device != 0, {{geom, p.geom, 56ull * n}, {ids, p.ids, 16ull * n}});
 }
 
 // rt_occluded for one precision: trace_rays' family, stream and counters; one byte a ray (host path: in q_ids).
@@ -752,52 +796,35 @@ template <class R>
 rt_status occluded(rt_context* c, const rt_trace_params* prm, const double* rays, uint32_t n, uint8_t* out,
                    hipStream_t st) {
   const bool f64 = sizeof(R) == 8;
-  const CompiledScene& cs = c->scene;
-  const SceneHeader& hdr = f64 ? cs.hdr64 : cs.hdr;
-  void* sbase = f64 ? c->scene64.ptr : c->scene32.ptr;
+  const SceneHeader& hdr = f64 ? c->scene.hdr64 : c->scene.hdr;
   const bool ordered = prm->traversal == RT_TRAV_ORDERED;
   const TraceFamily fam = trace_family(hdr, ordered, sizeof(typename WWord<R>::T));
-  if (!family_built(trace_render_family(fam)))
-    return set_err(c, RT_ERR_UNSUPPORTED,
-                   std::string("this build (RT_DEV_ONLY) has no ") + trace_family_name(fam) + " occlusion kernel");
   rt_status s;
+  if ((s = query_kernel_built(c, fam, "occlusion")) != RT_OK) return s;
   if ((s = query_scene(c, f64, st)) != RT_OK) return s;
   OcclParams<R> p{};
   p.rays = rays;
   p.out = out;
   if (!prm->on_device) {
-    if ((s = ensure(c, c->q_rays, 64ull * n)) != RT_OK) return s;
-    if ((s = ensure(c, c->q_ids, n)) != RT_OK) return s;
+    if ((s = stage(c, c->q_rays, 64ull * n, p.rays)) != RT_OK) return s;
+    if ((s = stage(c, c->q_ids, n, p.out)) != RT_OK) return s;
     RT_HIP(c, hipMemcpyAsync(c->q_rays.ptr, rays, 64ull * n, hipMemcpyHostToDevice, st));
-    p.rays = (const double*)c->q_rays.ptr;
-    p.out = (uint8_t*)c->q_ids.ptr;
   }
-  p.sc = dev_scene<R>(hdr, sbase);
-  if (fam == TF_WIDE_HBM && (s = wide_spill_area<R>(c, hdr, p.sc)) != RT_OK) return s;
-  if (ordered) p.sc.has_flat = p.sc.has_wide = 0;
-  p.sc.cam64 = nullptr;  // as trace_rays
+  if ((s = query_dev_scene<R>(c, fam, p.sc)) != RT_OK) return s;
+  if (ordered) p.sc.has_flat = p.sc.has_wide = 0;  // as trace_rays
   p.n = n;
   p.seed = prm->seed;
   p.seg_shards = (unsigned long long*)c->counters.ptr;
   launch_occluded<R>(p, fam, occlusion_early_exit(hdr, fam, sizeof(typename WWord<R>::T)), st);
-  RT_HIP(c, hipGetLastError());
-  c->last.launches++;
-  c->pending = true;  // as trace_rays
-  c->pend_stream = st;
-  if (!prm->on_device) {
-    RT_HIP(c, hipMemcpyAsync(out, p.out, n, hipMemcpyDeviceToHost, st));
-    RT_HIP(c, hipStreamSynchronize(st));
-    if ((s = settle(c)) != RT_OK) return s;
-  }
-  return RT_OK;
+  return query_done(c, st, true, prm->on_device != 0, {{out, p.out, n}});
 }
 
 // rt_camera_rays: the rays of samples [first_sample, first_sample + spp) of the tiles' pixels, n = npix * spp rows.
+// No scene, and no launch counted: rt_counters counts what traces.
 rt_status camera_rays(rt_context* c, const rt_camera_desc* cam, uint64_t seed, int32_t first_sample, uint32_t spp,
                       const std::vector<uint4>& tl, uint32_t npix, double* out, bool on_device, hipStream_t st) {
   rt_status s;
-  // as render: work of this context pending on another stream reads the pixel map and the camera view
-  if (c->pending && c->pend_stream != st && (s = wait_pending(c)) != RT_OK) return s;
+  if ((s = wait_other_stream(c, st)) != RT_OK) return s;  // (it reads the pixel map and the camera view)
   if ((s = pixel_map(c, tl, npix, st)) != RT_OK) return s;
   if ((s = camera_view(c, cam, st)) != RT_OK) return s;
   const uint64_t n = (uint64_t)npix * spp;
@@ -805,10 +832,7 @@ rt_status camera_rays(rt_context* c, const rt_camera_desc* cam, uint64_t seed, i
   p.pixmap = (const uint32_t*)c->pixmap.ptr;
   p.camx = (const CamDev*)c->camx.ptr;
   p.rays = out;
-  if (!on_device) {
-    if ((s = ensure(c, c->q_rays, 64ull * n)) != RT_OK) return s;
-    p.rays = (double*)c->q_rays.ptr;
-  }
+  if (!on_device && (s = stage(c, c->q_rays, 64ull * n, p.rays)) != RT_OK) return s;
   p.npix = npix;
   p.spp = spp;
   p.first_sample = (uint32_t)std::max(0, first_sample);
@@ -816,15 +840,7 @@ rt_status camera_rays(rt_context* c, const rt_camera_desc* cam, uint64_t seed, i
   p.cam_mode = c->cam_host.mode;
   p.seed = seed;
   launch_camera_rays(p, st);
-  RT_HIP(c, hipGetLastError());
-  c->pending = true;  // the launch reads the context's pixel map and camera view
-  c->pend_stream = st;
-  if (!on_device) {
-    RT_HIP(c, hipMemcpyAsync(out, p.rays, 64ull * n, hipMemcpyDeviceToHost, st));
-    RT_HIP(c, hipStreamSynchronize(st));
-    if ((s = settle(c)) != RT_OK) return s;
-  }
-  return RT_OK;
+  return query_done(c, st, false, on_device, {{out, p.rays, 64ull * n}});
 }
 
 // rt_render_aov for one precision: npix pixels (0 < npix * spp < 2^31) through the family aov_family gives the scene.
@@ -836,10 +852,8 @@ rt_status render_aov(rt_context* c, const rt_camera_desc* cam, const rt_aov_para
   const SceneHeader& hdr = f64 ? cs.hdr64 : cs.hdr;
   const bool ordered = prm->traversal == RT_TRAV_ORDERED;
   const TraceFamily fam = aov_family(hdr, ordered, sizeof(typename WWord<R>::T));
-  if (!family_built(trace_render_family(fam)))
-    return set_err(c, RT_ERR_UNSUPPORTED,
-                   std::string("this build (RT_DEV_ONLY) has no ") + trace_family_name(fam) + " feature-buffer kernel");
   rt_status s;
+  if ((s = query_kernel_built(c, fam, "feature-buffer")) != RT_OK) return s;
   if ((s = query_scene(c, f64, st)) != RT_OK) return s;
   if ((s = pixel_map(c, tl, npix, st)) != RT_OK) return s;
   if ((s = camera_view(c, cam, st)) != RT_OK) return s;
@@ -847,16 +861,14 @@ rt_status render_aov(rt_context* c, const rt_camera_desc* cam, const rt_aov_para
   p.feat = feat;
   p.ids = ids;
   if (!prm->on_device) {
-    if ((s = ensure(c, c->q_geom, 64ull * npix)) != RT_OK) return s;
-    if ((s = ensure(c, c->q_ids, 16ull * npix)) != RT_OK) return s;
-    p.feat = (double*)c->q_geom.ptr;
-    p.ids = (int32_t*)c->q_ids.ptr;
+    if ((s = stage(c, c->q_geom, 64ull * npix, p.feat)) != RT_OK) return s;
+    if ((s = stage(c, c->q_ids, 16ull * npix, p.ids)) != RT_OK) return s;
   }
-  p.sc = dev_scene<R>(hdr, f64 ? c->scene64.ptr : c->scene32.ptr);
-  if (fam == TF_WIDE_HBM && (s = wide_spill_area<R>(c, hdr, p.sc)) != RT_OK) return s;
+  if ((s = query_dev_scene<R>(c, fam, p.sc)) != RT_OK) return s;
+  // not the queries' rule: a scene with a picture texture leaves the flat program without being asked to (aov_family),
+  // and only the flat program; the wide tree is left as in a query
   if (fam != TF_FLAT) p.sc.has_flat = 0;
   if (ordered) p.sc.has_wide = 0;
-  p.sc.cam64 = nullptr;  // a near-edge quad hit is re-decided on the lane's own ray (quad_edge64), as in a query
   p.pixmap = (const uint32_t*)c->pixmap.ptr;
   p.camx = (const CamDev*)c->camx.ptr;
   p.idtab = (const int2*)c->ids.ptr;
@@ -870,26 +882,21 @@ rt_status render_aov(rt_context* c, const rt_camera_desc* cam, const rt_aov_para
   p.seed = prm->seed;
   p.seg_shards = (unsigned long long*)c->counters.ptr;
   launch_aov<R>(p, fam, st);
-  RT_HIP(c, hipGetLastError());
-  c->last.launches++;
-  c->pending = true;  // the segment counter (on the device) settles with rt_stats, as after a device-output render
-  c->pend_stream = st;
-  if (!prm->on_device) {
-    RT_HIP(c, hipMemcpyAsync(feat, p.feat, 64ull * npix, hipMemcpyDeviceToHost, st));
-    RT_HIP(c, hipMemcpyAsync(ids, p.ids, 16ull * npix, hipMemcpyDeviceToHost, st));
-    RT_HIP(c, hipStreamSynchronize(st));
-    if ((s = settle(c)) != RT_OK) return s;
-  }
-  return RT_OK;
+  return query_done(c, st, true, prm->on_device != 0, {{feat, p.feat, 64ull * npix}, {ids, p.ids, 16ull * npix}});
 }
 
-// What rt_camera_rays and rt_render_aov check of a camera and a tile list (the checks of rt_render_tiles)
-rt_status check_camera_tiles(rt_context* c, const rt_camera_desc* cam, const rt_tile* tiles, int32_t ntiles) {
+// ---------------------------------------------------------------- argument checks of the C entry points
+// Each check is written once; every entry point calls the ones it has in its own order (which error wins when several
+// apply differs between them, and stays: tests/test_gpu_query_contract.py).
+rt_status check_camera(rt_context* c, const rt_camera_desc* cam) {
   if (cam->mode < RT_CAM_PERSPECTIVE || cam->mode > RT_CAM_LENS)
     return set_err(c, RT_ERR_INVALID_ARGUMENT, "unknown camera mode");
   if (cam->image_width <= 0 || cam->image_height <= 0) return set_err(c, RT_ERR_INVALID_ARGUMENT, "empty image");
   if (cam->image_width > 65535 || cam->image_height > 65535)  // pixel positions are packed x | y << 16
     return set_err(c, RT_ERR_INVALID_ARGUMENT, "image wider or taller than 65535 pixels");
+  return RT_OK;
+}
+rt_status check_tiles(rt_context* c, const rt_camera_desc* cam, const rt_tile* tiles, int32_t ntiles) {
   for (int t = 0; t < ntiles; t++) {
     const rt_tile& tl = tiles[t];
     if (tl.x0 < 0 || tl.y0 < 0 || tl.width < 0 || tl.height < 0 || tl.x0 + tl.width > cam->image_width ||
@@ -897,6 +904,58 @@ rt_status check_camera_tiles(rt_context* c, const rt_camera_desc* cam, const rt_
       return set_err(c, RT_ERR_INVALID_ARGUMENT, "tile " + std::to_string(t) + " outside the image");
   }
   return RT_OK;
+}
+rt_status check_spp(rt_context* c, int32_t spp) {
+  return spp < 1 ? set_err(c, RT_ERR_INVALID_ARGUMENT, "spp must be positive") : RT_OK;
+}
+rt_status check_precision(rt_context* c, int32_t precision) {
+  if (precision != RT_PREC_F32 && precision != RT_PREC_F64)
+    return set_err(c, RT_ERR_INVALID_ARGUMENT, "unknown precision");
+  return RT_OK;
+}
+rt_status check_precision_traversal(rt_context* c, int32_t precision, int32_t traversal) {
+  rt_status s;
+  if ((s = check_precision(c, precision)) != RT_OK) return s;
+  if (traversal != RT_TRAV_AUTO && traversal != RT_TRAV_ORDERED)
+    return set_err(c, RT_ERR_INVALID_ARGUMENT, "unknown traversal");
+  return RT_OK;
+}
+rt_status check_nrays(rt_context* c, int64_t nrays) {
+  if (nrays < 0 || nrays >= (1ll << 31)) return set_err(c, RT_ERR_INVALID_ARGUMENT, "nrays outside [0, 2^31)");
+  return RT_OK;
+}
+rt_status check_npix_spp(rt_context* c, uint64_t npix, int32_t spp) {
+  if (npix * (uint64_t)spp >= (1ull << 31)) return set_err(c, RT_ERR_INVALID_ARGUMENT, "npix * spp outside [0, 2^31)");
+  return RT_OK;
+}
+rt_status check_scene(rt_context* c) {
+  return c->has_scene ? RT_OK : set_err(c, RT_ERR_NO_SCENE, "rt_scene_upload has not succeeded on this context");
+}
+
+// The stream of a call. Device pointers: NULL is the HIP null stream (torch's default stream), so work the caller
+// queues after this call on that stream -- a clone, a gather -- is ordered after it. Host pointers (the call returns
+// finished): NULL is the context's own non-blocking stream, so contexts driven from different host threads do not
+// serialise on the null stream.
+hipStream_t call_stream(rt_context* c, void* stream, bool on_device) {
+  return (stream == nullptr && !on_device) ? c->stream : (hipStream_t)stream;
+}
+
+// f() with running out of host memory reported as a status; any_exception: every other exception too (render<R>())
+template <class F>
+rt_status guarded(rt_context* c, bool any_exception, F&& f) {
+  try {
+    return f();
+  } catch (const std::bad_alloc&) {
+    return set_err(c, RT_ERR_OUT_OF_MEMORY, "out of host memory");
+  } catch (const std::exception& e) {
+    if (!any_exception) throw;
+    return set_err(c, RT_ERR_INVALID_ARGUMENT, e.what());
+  }
+}
+// ... and f(R()) for the float type R of a (checked) precision
+template <class F>
+rt_status by_precision(rt_context* c, int32_t precision, bool any_exception, F&& f) {
+  return guarded(c, any_exception, [&] { return precision == RT_PREC_F64 ? f(double()) : f(float()); });
 }
 
 }  // namespace
@@ -1047,107 +1106,75 @@ rt_status rt_render_tiles(rt_context* c, const rt_camera_desc* cam, const rt_ren
   if (!c) return set_err(nullptr, RT_ERR_INVALID_ARGUMENT, "null context");
   if (!cam || !prm || (!tiles && ntiles > 0) || ntiles < 0 || (!out_rgb && ntiles > 0))
     return set_err(c, RT_ERR_INVALID_ARGUMENT, "null argument");
-  if (!c->has_scene) return set_err(c, RT_ERR_NO_SCENE, "rt_scene_upload has not succeeded on this context");
-  if (cam->mode < RT_CAM_PERSPECTIVE || cam->mode > RT_CAM_LENS)
-    return set_err(c, RT_ERR_INVALID_ARGUMENT, "unknown camera mode");
-  if (cam->image_width <= 0 || cam->image_height <= 0) return set_err(c, RT_ERR_INVALID_ARGUMENT, "empty image");
-  if (cam->image_width > 65535 || cam->image_height > 65535)  // pixel positions are packed x | y << 16
-    return set_err(c, RT_ERR_INVALID_ARGUMENT, "image wider or taller than 65535 pixels");
-  if (prm->spp <= 0) return set_err(c, RT_ERR_INVALID_ARGUMENT, "spp must be positive");
-  if (prm->precision != RT_PREC_F32 && prm->precision != RT_PREC_F64)
-    return set_err(c, RT_ERR_INVALID_ARGUMENT, "unknown precision");
-  for (int t = 0; t < ntiles; t++) {
-    const rt_tile& tl = tiles[t];
-    if (tl.x0 < 0 || tl.y0 < 0 || tl.width < 0 || tl.height < 0 || tl.x0 + tl.width > cam->image_width ||
-        tl.y0 + tl.height > cam->image_height)
-      return set_err(c, RT_ERR_INVALID_ARGUMENT, "tile " + std::to_string(t) + " outside the image");
-  }
+  rt_status s;
+  if ((s = check_scene(c)) != RT_OK) return s;
+  if ((s = check_camera(c, cam)) != RT_OK) return s;
+  if ((s = check_spp(c, prm->spp)) != RT_OK) return s;
+  if ((s = check_precision(c, prm->precision)) != RT_OK) return s;
+  if ((s = check_tiles(c, cam, tiles, ntiles)) != RT_OK) return s;
   RT_HIP(c, hipSetDevice(c->device));
-  // Device output: NULL is the HIP null stream (torch's default stream), so work the caller queues
-  // after this call on that stream -- a clone, a gather -- is ordered after the render. Host output
-  // (the call returns the finished image): NULL is the context's own non-blocking stream, so contexts
-  // driven from different host threads do not serialise on the null stream.
-  hipStream_t st = (stream == nullptr && !out_is_device) ? c->stream : (hipStream_t)stream;
-  try {
-    if (prm->precision == RT_PREC_F64) return render<double>(c, cam, prm, tiles, ntiles, out_rgb, out_is_device, st);
-    return render<float>(c, cam, prm, tiles, ntiles, out_rgb, out_is_device, st);
-  } catch (const std::bad_alloc&) {
-    return set_err(c, RT_ERR_OUT_OF_MEMORY, "out of host memory");
-  } catch (const std::exception& e) {
-    return set_err(c, RT_ERR_INVALID_ARGUMENT, e.what());
-  }
+  hipStream_t st = call_stream(c, stream, out_is_device != 0);
+  return by_precision(c, prm->precision, true, [&](auto r) {
+    return render<decltype(r)>(c, cam, prm, tiles, ntiles, out_rgb, out_is_device, st);
+  });
 }
 
 rt_status rt_trace_rays(rt_context* c, const rt_trace_params* prm, const double* rays, int64_t nrays, double* out_geom,
                         int32_t* out_ids, void* stream) {
   if (!c) return set_err(nullptr, RT_ERR_INVALID_ARGUMENT, "null context");
   if (!prm || !rays || !out_geom || !out_ids) return set_err(c, RT_ERR_INVALID_ARGUMENT, "null argument");
-  if (nrays < 0 || nrays >= (1ll << 31)) return set_err(c, RT_ERR_INVALID_ARGUMENT, "nrays outside [0, 2^31)");
-  if (prm->precision != RT_PREC_F32 && prm->precision != RT_PREC_F64)
-    return set_err(c, RT_ERR_INVALID_ARGUMENT, "unknown precision");
-  if (prm->traversal != RT_TRAV_AUTO && prm->traversal != RT_TRAV_ORDERED)
-    return set_err(c, RT_ERR_INVALID_ARGUMENT, "unknown traversal");
+  rt_status s;
+  if ((s = check_nrays(c, nrays)) != RT_OK) return s;
+  if ((s = check_precision_traversal(c, prm->precision, prm->traversal)) != RT_OK) return s;
   // the kernel reads a ray and writes its ids as 16-byte words
   if (prm->on_device && (((uintptr_t)rays | (uintptr_t)out_ids) % 16 != 0 || (uintptr_t)out_geom % 8 != 0))
     return set_err(c, RT_ERR_INVALID_ARGUMENT, "device rays and out_ids must be 16-byte aligned, out_geom 8-byte");
-  if (!c->has_scene) return set_err(c, RT_ERR_NO_SCENE, "rt_scene_upload has not succeeded on this context");
+  if ((s = check_scene(c)) != RT_OK) return s;
   if (nrays == 0) return RT_OK;
   RT_HIP(c, hipSetDevice(c->device));
-  // the stream as rt_render_tiles takes it: NULL is the null stream for device pointers, the context's own otherwise
-  hipStream_t st = (stream == nullptr && !prm->on_device) ? c->stream : (hipStream_t)stream;
-  try {
-    if (prm->precision == RT_PREC_F64) return trace_rays<double>(c, prm, rays, (uint32_t)nrays, out_geom, out_ids, st);
-    return trace_rays<float>(c, prm, rays, (uint32_t)nrays, out_geom, out_ids, st);
-  } catch (const std::bad_alloc&) {
-    return set_err(c, RT_ERR_OUT_OF_MEMORY, "out of host memory");
-  }
+  hipStream_t st = call_stream(c, stream, prm->on_device != 0);
+  return by_precision(c, prm->precision, false, [&](auto r) {
+    return trace_rays<decltype(r)>(c, prm, rays, (uint32_t)nrays, out_geom, out_ids, st);
+  });
 }
 
 rt_status rt_occluded(rt_context* c, const rt_trace_params* prm, const double* rays, int64_t nrays,
                       uint8_t* out_occluded, void* stream) {
   if (!c) return set_err(nullptr, RT_ERR_INVALID_ARGUMENT, "null context");
   if (!prm || !rays || !out_occluded) return set_err(c, RT_ERR_INVALID_ARGUMENT, "null argument");
-  if (nrays < 0 || nrays >= (1ll << 31)) return set_err(c, RT_ERR_INVALID_ARGUMENT, "nrays outside [0, 2^31)");
-  if (prm->precision != RT_PREC_F32 && prm->precision != RT_PREC_F64)
-    return set_err(c, RT_ERR_INVALID_ARGUMENT, "unknown precision");
-  if (prm->traversal != RT_TRAV_AUTO && prm->traversal != RT_TRAV_ORDERED)
-    return set_err(c, RT_ERR_INVALID_ARGUMENT, "unknown traversal");
+  rt_status s;
+  if ((s = check_nrays(c, nrays)) != RT_OK) return s;
+  if ((s = check_precision_traversal(c, prm->precision, prm->traversal)) != RT_OK) return s;
   if (prm->on_device && (uintptr_t)rays % 16 != 0)  // the kernel reads a ray as 16-byte words
     return set_err(c, RT_ERR_INVALID_ARGUMENT, "device rays must be 16-byte aligned");
-  if (!c->has_scene) return set_err(c, RT_ERR_NO_SCENE, "rt_scene_upload has not succeeded on this context");
+  if ((s = check_scene(c)) != RT_OK) return s;
   if (nrays == 0) return RT_OK;
   RT_HIP(c, hipSetDevice(c->device));
-  // the stream as rt_trace_rays takes it
-  hipStream_t st = (stream == nullptr && !prm->on_device) ? c->stream : (hipStream_t)stream;
-  try {
-    if (prm->precision == RT_PREC_F64) return occluded<double>(c, prm, rays, (uint32_t)nrays, out_occluded, st);
-    return occluded<float>(c, prm, rays, (uint32_t)nrays, out_occluded, st);
-  } catch (const std::bad_alloc&) {
-    return set_err(c, RT_ERR_OUT_OF_MEMORY, "out of host memory");
-  }
+  hipStream_t st = call_stream(c, stream, prm->on_device != 0);
+  return by_precision(c, prm->precision, false, [&](auto r) {
+    return occluded<decltype(r)>(c, prm, rays, (uint32_t)nrays, out_occluded, st);
+  });
 }
 
 rt_status rt_camera_rays(rt_context* c, const rt_camera_desc* cam, uint64_t seed, int32_t first_sample, int32_t spp,
                          const rt_tile* tiles, int32_t ntiles, double* out_rays, int32_t on_device, void* stream) {
   if (!c) return set_err(nullptr, RT_ERR_INVALID_ARGUMENT, "null context");
   if (!cam || !tiles || !out_rays || ntiles < 0) return set_err(c, RT_ERR_INVALID_ARGUMENT, "null argument");
-  if (spp < 1) return set_err(c, RT_ERR_INVALID_ARGUMENT, "spp must be positive");
+  rt_status s;
+  if ((s = check_spp(c, spp)) != RT_OK) return s;
   if (on_device && (uintptr_t)out_rays % 16 != 0)  // the kernel writes a ray as 16-byte words
     return set_err(c, RT_ERR_INVALID_ARGUMENT, "device out_rays must be 16-byte aligned");
-  rt_status s;
-  if ((s = check_camera_tiles(c, cam, tiles, ntiles)) != RT_OK) return s;
-  try {
+  if ((s = check_camera(c, cam)) != RT_OK) return s;
+  if ((s = check_tiles(c, cam, tiles, ntiles)) != RT_OK) return s;
+  return guarded(c, false, [&]() -> rt_status {
     uint64_t npix = 0;
     const std::vector<uint4> tl = pack_tiles(tiles, ntiles, npix);
-    if (npix * (uint64_t)spp >= (1ull << 31)) return set_err(c, RT_ERR_INVALID_ARGUMENT, "npix * spp outside [0, 2^31)");
+    if ((s = check_npix_spp(c, npix, spp)) != RT_OK) return s;
     if (npix == 0) return RT_OK;
     RT_HIP(c, hipSetDevice(c->device));
-    // the stream as rt_trace_rays takes it: NULL is the null stream for device pointers, the context's own otherwise
-    hipStream_t st = (stream == nullptr && !on_device) ? c->stream : (hipStream_t)stream;
+    hipStream_t st = call_stream(c, stream, on_device != 0);
     return camera_rays(c, cam, seed, first_sample, (uint32_t)spp, tl, (uint32_t)npix, out_rays, on_device != 0, st);
-  } catch (const std::bad_alloc&) {
-    return set_err(c, RT_ERR_OUT_OF_MEMORY, "out of host memory");
-  }
+  });
 }
 
 rt_status rt_render_aov(rt_context* c, const rt_camera_desc* cam, const rt_aov_params* prm, const rt_tile* tiles,
@@ -1155,29 +1182,23 @@ rt_status rt_render_aov(rt_context* c, const rt_camera_desc* cam, const rt_aov_p
   if (!c) return set_err(nullptr, RT_ERR_INVALID_ARGUMENT, "null context");
   if (!cam || !prm || !tiles || !out_feat || !out_ids || ntiles < 0)
     return set_err(c, RT_ERR_INVALID_ARGUMENT, "null argument");
-  if (prm->spp < 1) return set_err(c, RT_ERR_INVALID_ARGUMENT, "spp must be positive");
-  if (prm->precision != RT_PREC_F32 && prm->precision != RT_PREC_F64)
-    return set_err(c, RT_ERR_INVALID_ARGUMENT, "unknown precision");
-  if (prm->traversal != RT_TRAV_AUTO && prm->traversal != RT_TRAV_ORDERED)
-    return set_err(c, RT_ERR_INVALID_ARGUMENT, "unknown traversal");
+  rt_status s;
+  if ((s = check_spp(c, prm->spp)) != RT_OK) return s;
+  if ((s = check_precision_traversal(c, prm->precision, prm->traversal)) != RT_OK) return s;
   if (prm->on_device && ((uintptr_t)out_feat | (uintptr_t)out_ids) % 16 != 0)  // both are written as 16-byte words
     return set_err(c, RT_ERR_INVALID_ARGUMENT, "device out_feat and out_ids must be 16-byte aligned");
-  rt_status s;
-  if ((s = check_camera_tiles(c, cam, tiles, ntiles)) != RT_OK) return s;
-  if (!c->has_scene) return set_err(c, RT_ERR_NO_SCENE, "rt_scene_upload has not succeeded on this context");
-  try {
+  if ((s = check_camera(c, cam)) != RT_OK) return s;
+  if ((s = check_tiles(c, cam, tiles, ntiles)) != RT_OK) return s;
+  if ((s = check_scene(c)) != RT_OK) return s;
+  return by_precision(c, prm->precision, false, [&](auto r) -> rt_status {
     uint64_t npix = 0;
     const std::vector<uint4> tl = pack_tiles(tiles, ntiles, npix);
-    if (npix * (uint64_t)prm->spp >= (1ull << 31))
-      return set_err(c, RT_ERR_INVALID_ARGUMENT, "npix * spp outside [0, 2^31)");
+    if ((s = check_npix_spp(c, npix, prm->spp)) != RT_OK) return s;
     if (npix == 0) return RT_OK;
     RT_HIP(c, hipSetDevice(c->device));
-    hipStream_t st = (stream == nullptr && !prm->on_device) ? c->stream : (hipStream_t)stream;
-    if (prm->precision == RT_PREC_F64) return render_aov<double>(c, cam, prm, tl, (uint32_t)npix, out_feat, out_ids, st);
-    return render_aov<float>(c, cam, prm, tl, (uint32_t)npix, out_feat, out_ids, st);
-  } catch (const std::bad_alloc&) {
-    return set_err(c, RT_ERR_OUT_OF_MEMORY, "out of host memory");
-  }
+    hipStream_t st = call_stream(c, stream, prm->on_device != 0);
+    return render_aov<decltype(r)>(c, cam, prm, tl, (uint32_t)npix, out_feat, out_ids, st);
+  });
 }
 
 int32_t rt_trace_family(rt_context* c, int32_t precision, int32_t traversal) {

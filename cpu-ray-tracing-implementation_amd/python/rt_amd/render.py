@@ -87,34 +87,11 @@ class Context:
         A C-contiguous numpy array takes the host path and returns numpy arrays once they are filled. A float64
         torch tensor on the context's device takes the device path: the call is ordered on `stream` (a
         torch.cuda.Stream or a raw handle; default torch's current stream) and returns tensors on that device."""
-        prm = abi.rt_trace_params(seed=seed, precision=precision, traversal=traversal, on_device=0)
-        if isinstance(rays, np.ndarray):
-            if rays.dtype != np.float64 or rays.ndim != 2 or rays.shape[1] != 8 or not rays.flags.c_contiguous:
-                raise ValueError("rays: a C-contiguous (n, 8) float64 array")
-            n = rays.shape[0]
-            geom = np.empty((n, 7), dtype=np.float64)
-            ids = np.empty((n, 4), dtype=np.int32)
-            # (an empty array still hands over valid pointers: the call checks its arguments and launches nothing)
-            pad = np.zeros(8)
-            self._check(self.lib.rt_trace_rays(self.h, ctypes.byref(prm), rays.ctypes.data if n else pad.ctypes.data, n,
-                                               geom.ctypes.data if n else pad.ctypes.data,
-                                               ids.ctypes.data if n else pad.ctypes.data,
-                                               ctypes.c_void_p(self._stream_handle(stream) if stream else 0)))
-            return geom, ids
-        import torch
-        if not (isinstance(rays, torch.Tensor) and rays.is_cuda and rays.dtype == torch.float64 and rays.dim() == 2 and
-                rays.shape[1] == 8 and rays.is_contiguous()):
-            raise ValueError("rays: a contiguous (n, 8) float64 numpy array or CUDA/HIP torch tensor")
-        n = rays.shape[0]
-        geom = torch.empty((max(n, 1), 7), dtype=torch.float64, device=rays.device)[:n]
-        ids = torch.empty((max(n, 1), 4), dtype=torch.int32, device=rays.device)[:n]
-        prm.on_device = 1
-        if stream is None:
-            stream = torch.cuda.current_stream(rays.device)
-        src = rays if n else torch.zeros((1, 8), dtype=torch.float64, device=rays.device)
-        self._check(self.lib.rt_trace_rays(self.h, ctypes.byref(prm), ctypes.c_void_p(src.data_ptr()), n,
-                                           ctypes.c_void_p(geom.data_ptr()), ctypes.c_void_p(ids.data_ptr()),
-                                           ctypes.c_void_p(self._stream_handle(stream))))
+        dev, n, src, sp, stream = self._ray_source(rays, stream)
+        prm = abi.rt_trace_params(seed=seed, precision=precision, traversal=traversal, on_device=int(dev is not None))
+        geom, gp = self._output(n, (7,), "float64", dev)
+        ids, ip = self._output(n, (4,), "int32", dev)
+        self._check(self.lib.rt_trace_rays(self.h, ctypes.byref(prm), sp, n, gp, ip, stream))
         return geom, ids
 
     def occluded(self, rays, precision=abi.RT_PREC_F64, traversal=0, seed=1, stream=None, out=None):
@@ -126,37 +103,58 @@ class Context:
         context's device takes the device path, ordered on `stream` (default torch's current stream), and returns a
         torch.uint8 tensor on that device -- the first n bytes of `out` where one is given (device path only: a
         contiguous torch.uint8 tensor of at least n elements on that device; the call writes nothing past them)."""
-        prm = abi.rt_trace_params(seed=seed, precision=precision, traversal=traversal, on_device=0)
+        dev, n, src, sp, stream = self._ray_source(rays, stream)
+        prm = abi.rt_trace_params(seed=seed, precision=precision, traversal=traversal, on_device=int(dev is not None))
+        if out is None:
+            out, op = self._output(n, (), "uint8", dev)
+        elif dev is None:
+            raise ValueError("out: only with the device path")
+        else:
+            import torch
+            if not (isinstance(out, torch.Tensor) and out.device == dev and out.dtype == torch.uint8 and
+                    out.dim() == 1 and out.is_contiguous() and out.shape[0] >= max(n, 1)):
+                raise ValueError("out: a contiguous 1-D torch.uint8 tensor of at least n elements on the rays' device")
+            # (the whole tensor's pointer: an empty slice has none, and the call checks its arguments even for n = 0)
+            out, op = out[:n], out.data_ptr()
+        self._check(self.lib.rt_occluded(self.h, ctypes.byref(prm), sp, n, op, stream))
+        return out
+
+    def _ray_source(self, rays, stream):
+        """What trace_rays and occluded make of their `rays` and `stream`: (the rays' torch device, or None for the
+        host path; n; the array to read -- one padding row for n = 0: an empty array still hands over a valid pointer,
+        since the call checks its arguments and launches nothing -- and its pointer; the stream handle or None)."""
         if isinstance(rays, np.ndarray):
             if rays.dtype != np.float64 or rays.ndim != 2 or rays.shape[1] != 8 or not rays.flags.c_contiguous:
                 raise ValueError("rays: a C-contiguous (n, 8) float64 array")
-            if out is not None:
-                raise ValueError("out: only with the device path")
             n = rays.shape[0]
-            out = np.empty((max(n, 1),), dtype=np.uint8)[:n]
-            pad = np.zeros(8)  # (an empty array still hands over valid pointers, as trace_rays)
-            self._check(self.lib.rt_occluded(self.h, ctypes.byref(prm), rays.ctypes.data if n else pad.ctypes.data, n,
-                                             out.ctypes.data if n else pad.ctypes.data,
-                                             ctypes.c_void_p(self._stream_handle(stream) if stream else 0)))
-            return out
+            src = rays if n else np.zeros((1, 8))
+            return None, n, src, src.ctypes.data, self._stream_handle(stream) if stream else None
         import torch
         if not (isinstance(rays, torch.Tensor) and rays.is_cuda and rays.dtype == torch.float64 and rays.dim() == 2 and
                 rays.shape[1] == 8 and rays.is_contiguous()):
             raise ValueError("rays: a contiguous (n, 8) float64 numpy array or CUDA/HIP torch tensor")
         n = rays.shape[0]
-        if out is None:
-            out = torch.empty((max(n, 1),), dtype=torch.uint8, device=rays.device)
-        elif not (isinstance(out, torch.Tensor) and out.device == rays.device and out.dtype == torch.uint8 and
-                  out.dim() == 1 and out.is_contiguous() and out.shape[0] >= max(n, 1)):
-            raise ValueError("out: a contiguous 1-D torch.uint8 tensor of at least n elements on the rays' device")
-        prm.on_device = 1
-        if stream is None:
-            stream = torch.cuda.current_stream(rays.device)
         src = rays if n else torch.zeros((1, 8), dtype=torch.float64, device=rays.device)
-        # (the whole tensor's pointer: an empty slice has none, and the call checks its arguments even for n = 0)
-        self._check(self.lib.rt_occluded(self.h, ctypes.byref(prm), ctypes.c_void_p(src.data_ptr()), n,
-                                         ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(self._stream_handle(stream))))
-        return out[:n]
+        return rays.device, n, src, src.data_ptr(), self._torch_stream(stream, rays.device)
+
+    @staticmethod
+    def _output(n, cols, dtype, dev, fill=None):
+        """An output of n rows of shape `cols`: a numpy array (dev None) or a torch tensor on `dev`, uninitialised or
+        filled with `fill`, and the pointer to hand over -- of a buffer of at least one row, of which the output is
+        the first n, so that the pointer is valid for n = 0 too."""
+        shape = (n or 1,) + cols
+        if dev is None:
+            base = np.empty(shape, dtype) if fill is None else np.full(shape, fill, dtype)
+            return (base if n else base[:0]), base.ctypes.data
+        import torch
+        dt = getattr(torch, dtype)
+        base = torch.empty(shape, dtype=dt, device=dev) if fill is None else torch.full(shape, fill, dtype=dt, device=dev)
+        return (base if n else base[:0]), base.data_ptr()
+
+    def _torch_stream(self, stream, dev):
+        """The handle of `stream`, a torch.cuda.Stream or a raw handle; None: torch's current stream on `dev`."""
+        import torch
+        return self._stream_handle(torch.cuda.current_stream(dev) if stream is None else stream)
 
     def _tiles(self, cam, tiles):
         """(ctypes tile array, count, pixels, whether it is the whole image as one tile)."""
@@ -172,21 +170,20 @@ class Context:
         (default: the whole image, row-major). Needs no scene. device=False: a numpy array; device=True: a torch
         tensor on the context's device, the call ordered on `stream` (default torch's current stream)."""
         arr, nt, npix, _ = self._tiles(cam, tiles)
-        n = npix * spp
+        dev, sp = self._output_device(device, stream)
+        out, op = self._output(npix * spp, (8,), "float64", dev)
+        self._check(self.lib.rt_camera_rays(self.h, ctypes.byref(cam), seed, first_sample, spp, arr, nt,
+                                            op, 1 if device else 0, sp))
+        return out
+
+    def _output_device(self, device, stream):
+        """What camera_rays and render_aov make of `device` and `stream`: (the context's torch device and the stream
+        handle, or None twice for host outputs)."""
         if not device:
-            out = np.empty((max(n, 1), 8), dtype=np.float64)[:n]
-            self._check(self.lib.rt_camera_rays(self.h, ctypes.byref(cam), seed, first_sample, spp, arr, nt,
-                                                ctypes.c_void_p(out.ctypes.data), 0, ctypes.c_void_p(0)))
-            return out
+            return None, None
         import torch
         dev = torch.device("cuda", self.device)
-        out = torch.empty((max(n, 1), 8), dtype=torch.float64, device=dev)[:n]
-        if stream is None:
-            stream = torch.cuda.current_stream(dev)
-        self._check(self.lib.rt_camera_rays(self.h, ctypes.byref(cam), seed, first_sample, spp, arr, nt,
-                                            ctypes.c_void_p(out.data_ptr()), 1,
-                                            ctypes.c_void_p(self._stream_handle(stream))))
-        return out
+        return dev, self._torch_stream(stream, dev)
 
     def render_aov(self, cam, spp, seed=1, precision=abi.RT_PREC_F32, traversal=0, first_sample=0, tiles=None,
                    device=False, stream=None):
@@ -198,20 +195,10 @@ class Context:
         arr, nt, npix, full = self._tiles(cam, tiles)
         prm = abi.rt_aov_params(seed=seed, spp=spp, first_sample=first_sample, precision=precision,
                                 traversal=traversal, on_device=1 if device else 0)
-        if not device:
-            feat = np.zeros((max(npix, 1), 8), dtype=np.float64)[:npix]
-            ids = np.full((max(npix, 1), 4), -1, dtype=np.int32)[:npix]
-            fp, ip, sp = feat.ctypes.data, ids.ctypes.data, 0
-        else:
-            import torch
-            dev = torch.device("cuda", self.device)
-            feat = torch.zeros((max(npix, 1), 8), dtype=torch.float64, device=dev)[:npix]
-            ids = torch.full((max(npix, 1), 4), -1, dtype=torch.int32, device=dev)[:npix]
-            if stream is None:
-                stream = torch.cuda.current_stream(dev)
-            fp, ip, sp = feat.data_ptr(), ids.data_ptr(), self._stream_handle(stream)
-        self._check(self.lib.rt_render_aov(self.h, ctypes.byref(cam), ctypes.byref(prm), arr, nt, ctypes.c_void_p(fp),
-                                           ctypes.c_void_p(ip), ctypes.c_void_p(sp)))
+        dev, sp = self._output_device(device, stream)
+        feat, fp = self._output(npix, (8,), "float64", dev, fill=0.0)
+        ids, ip = self._output(npix, (4,), "int32", dev, fill=-1)
+        self._check(self.lib.rt_render_aov(self.h, ctypes.byref(cam), ctypes.byref(prm), arr, nt, fp, ip, sp))
         shape = (cam.image_height, cam.image_width) if full else (npix,)
         return dict(albedo=feat[:, 0:3].reshape(*shape, 3), normal=feat[:, 3:6].reshape(*shape, 3),
                     depth=feat[:, 6].reshape(*shape), hit=feat[:, 7].reshape(*shape), ids=ids.reshape(*shape, 4))
