@@ -15,8 +15,10 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
 #include <map>
 #include <mutex>
+#include <string>
 #include <tuple>
 #include <type_traits>
 
@@ -805,7 +807,18 @@ __device__ bool shade(const Params<R>& p, PS& s, R t, uint32_t e, int32_t inst, 
         new_d = dir;
       }
       new_o = pw;
-      if (s.bounce + 1 >= p.max_depth) done = true;  // ray_color(.., 0) returns 0 (camera.h:194)
+      if (s.bounce + 1 >= p.max_depth) {  // ray_color(.., 0) returns 0 (camera.h:194) ...
+        done = true;
+        // ... which the caller multiplies by this bounce's weight (camera.h:238): 0, but NaN where the weight is the
+        // 0 / 0 of a zero mixture pdf (a base-class light). fp64 keeps the reference's NaN; fp32 ended that path above.
+        // Not in the LL and NL forms: their scenes have an axis-aligned quad light or none, where a zero mixture pdf
+        // is a measure-zero event, and the three multiplies cost the flat LL kernel 0.5 % (C2 fp64 23.01 -> 23.13
+        // ms/frame, four alternating runs each, spread 0.02).
+        if constexpr (sizeof(R) == 8 && !LL && !NL) {
+          add = s.thr() * R(0);
+          has_add = true;
+        }
+      }
       {
         const V<R> thr = s.thr();
         if (thr.x == R(0) && thr.y == R(0) && thr.z == R(0)) done = true;
@@ -2001,8 +2014,45 @@ uint32_t resident_blocks(const void* kern, int dev, size_t lds) {
 // lanes of the last persistent launch on this host thread (rt_counters.grid_lanes)
 thread_local uint64_t t_grid_lanes = 0;
 
-template <class KernelT, class R>
+// The tag of a path kernel (rt_dev_last_kernel): its traversal policy with every template argument in order (the
+// precision first, as f32 / f64; bools as 0 / 1), "camx" for the extended camera and texture form, and the schedule:
+// "WideTrav<f64,0,1,1,0,1,1,0> persist", "LinearTrav<f32,1,1,1,0> camx step". Host code only.
+template <class R, class... A>
+std::string trav_tag(const char* name, A... args) {
+  std::string s = std::string(name) + (sizeof(R) == 8 ? "<f64" : "<f32");
+  ((s += "," + std::to_string((int)args)), ...);
+  return s + ">";
+}
+template <class Trav>
+struct TravName;
+template <class R, bool SPH, bool TRI, bool VOL, bool LLI>
+struct TravName<LinearTrav<R, SPH, TRI, VOL, LLI>> {
+  static std::string get() { return trav_tag<R>("LinearTrav", SPH, TRI, VOL, LLI); }
+};
+template <class R, bool TLDS, bool LL>
+struct TravName<FlatTrav<R, TLDS, LL>> {
+  static std::string get() { return trav_tag<R>("FlatTrav", TLDS, LL); }
+};
+template <class R, int STACK, bool LDSN>
+struct TravName<StackTrav<R, STACK, LDSN>> {
+  static std::string get() { return trav_tag<R>("StackTrav", STACK, LDSN); }
+};
+template <class R, bool SPH, bool TRI, bool QUAD, bool MOV, bool LDSN, bool LL, bool NL>
+struct TravName<WideTrav<R, SPH, TRI, QUAD, MOV, LDSN, LL, NL>> {
+  static std::string get() { return trav_tag<R>("WideTrav", SPH, TRI, QUAD, MOV, LDSN, LL, NL); }
+};
+template <class Trav, bool CAMX>
+const char* kernel_tag(bool persist) {  // built once per kernel: a wavefront render launches its kernel many times
+  static const std::string tag[2] = {TravName<Trav>::get() + (CAMX ? " camx step" : " step"),
+                                     TravName<Trav>::get() + (CAMX ? " camx persist" : " persist")};
+  return tag[persist ? 1 : 0].c_str();
+}
+// tag of the last path kernel launched on this host thread
+thread_local const char* t_kernel = "";
+
+template <class Trav, bool CAMX, class KernelT, class R>
 void launch_one(KernelT kern, Params<R> p, uint32_t grid, hipStream_t st, size_t lds = 0) {
+  t_kernel = kernel_tag<Trav, CAMX>(p.persist != 0);
   if (p.persist) {  // as many blocks as the chip holds resident; lanes pull items
     int dev = 0;
     const uint32_t res = hipGetDevice(&dev) == hipSuccess ? resident_blocks((const void*)kern, dev, lds) : 0;
@@ -2050,12 +2100,13 @@ void launch_wide_k(const Params<R>& p, uint32_t grid, hipStream_t st) {
   const size_t full = wide_lds_bytes(p.sc, true);
   const uint32_t spill_grid = p.sc.wide_spill ? std::min<uint32_t>(grid, p.sc.spill_lanes / kBlock) : grid;
   if (wide_tree_in_lds(p.sc.n_wnodes, p.sc.n_wprim_words, p.sc.wide_stack, sizeof(typename WWord<R>::T))) {
-    launch_one(k_persist_occ<R, WideTrav<R, SPH, TRI, QUAD, MOV, true, LL, NL>, false>, p, grid, st, full);
+    using InLds = WideTrav<R, SPH, TRI, QUAD, MOV, true, LL, NL>;
+    launch_one<InLds, false>(k_persist_occ<R, InLds, false>, p, grid, st, full);
     return;
   }
   // the spill area holds spill_lanes lanes: never launch more (the resident grid is below it)
-  launch_one(k_persist_occ<R, WideTrav<R, SPH, TRI, QUAD, MOV, false, LL, NL>, false>, p, spill_grid, st,
-             wide_lds_bytes(p.sc, false));
+  using InHbm = WideTrav<R, SPH, TRI, QUAD, MOV, false, LL, NL>;
+  launch_one<InHbm, false>(k_persist_occ<R, InHbm, false>, p, spill_grid, st, wide_lds_bytes(p.sc, false));
 }
 // Kernel for the primitive kinds of the scene: spheres only (RTOW), triangles only or triangles and
 // quads (meshes, the C4 stand-in with its light), or all.
@@ -2082,22 +2133,22 @@ void launch_k(const Params<R>& p, uint32_t grid, hipStream_t st) {
   if (camx && !Trav::kFlat) {
     if constexpr (!Trav::kFlat) {
       if (p.persist)
-        launch_one(k_persist_occ<R, Trav, true>, p, grid, st);
+        launch_one<Trav, true>(k_persist_occ<R, Trav, true>, p, grid, st);
       else
-        launch_one(k_step_occ<R, Trav, true>, p, grid, st);
+        launch_one<Trav, true>(k_step_occ<R, Trav, true>, p, grid, st);
     }
     return;
   }
   if (p.persist) {
     if constexpr (Trav::kWaves > 1)
-      launch_one(k_persist_occ<R, Trav, false>, p, grid, st);
+      launch_one<Trav, false>(k_persist_occ<R, Trav, false>, p, grid, st);
     else
-      launch_one(k_persist<R, Trav, false>, p, grid, st);
+      launch_one<Trav, false>(k_persist<R, Trav, false>, p, grid, st);
   } else {
     if constexpr (Trav::kWaves > 1)
-      launch_one(k_step_occ<R, Trav, false>, p, grid, st);
+      launch_one<Trav, false>(k_step_occ<R, Trav, false>, p, grid, st);
     else
-      launch_one(k_step<R, Trav, false>, p, grid, st);
+      launch_one<Trav, false>(k_step<R, Trav, false>, p, grid, st);
   }
 }
 
@@ -2213,6 +2264,7 @@ void launch_step(const LaunchParams<R>& lp, KernelFamily fam, bool ll, bool nl, 
 }
 
 uint64_t last_grid_lanes() { return t_grid_lanes; }
+const char* last_kernel() { return t_kernel; }
 
 // The three query launches: with_query_family's traversal of `fam`, each in its own kernel.
 template <class R>
@@ -2343,5 +2395,11 @@ void rt_dev_wide_stats(unsigned long long out[10]) {
   (void)hipMemcpyToSymbol(HIP_SYMBOL(rtd::g_wide_stats), z, sizeof(z));
 }
 #endif
+// The tag of the last path kernel launch_step launched on the calling host thread (kernel_tag above), "" before the
+// first; copied into buf[0, n) and always terminated. Host only; for tests and scripts, not in rt_hip.h.
+void rt_dev_last_kernel(char* buf, size_t n) {
+  if (!buf || n == 0) return;
+  std::snprintf(buf, n, "%s", rtd::last_kernel());
+}
 
 }  // extern "C"

@@ -97,6 +97,7 @@ template <class R>
 void launch_step(const LaunchParams<R>& p, KernelFamily fam, bool ll, bool nl, bool lli, int stack, uint32_t grid,
                  hipStream_t st);
 uint64_t last_grid_lanes();  // lanes of the last persistent launch_step on this host thread
+const char* last_kernel();   // tag of the kernel the last launch_step on this host thread launched ("" before the first)
 
 // wavefront schedule: the first camera ray of every slot; live-slot count and compaction
 template <class R>

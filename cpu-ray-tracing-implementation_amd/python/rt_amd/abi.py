@@ -183,6 +183,9 @@ def load():
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
+        # a development entry point beside the C ABI (not in include/rt_hip.h): Context.last_kernel
+        lib.rt_dev_last_kernel.restype = None
+        lib.rt_dev_last_kernel.argtypes = [ctypes.c_char_p, ctypes.c_size_t]
         if lib.rt_abi_version() != ABI_VERSION:
             raise RuntimeError(f"{path} has ABI {lib.rt_abi_version()}, this binding expects {ABI_VERSION}: rebuild")
         _lib = lib

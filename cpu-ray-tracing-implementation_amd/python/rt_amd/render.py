@@ -71,6 +71,14 @@ class Context:
         self.render_tiles(cam, p, tiles, out.ctypes.data, 0)
         return out.reshape(cam.image_height, cam.image_width, 3) if full else out
 
+    def last_kernel(self):
+        """The tag of the path kernel the last render on this host thread launched (rt_dev_last_kernel): the
+        traversal policy with its template arguments, "camx" for the extended form, and the schedule, e.g.
+        "FlatTrav<f64,1,1> persist"; "" before the first render. Per host thread, not per context."""
+        buf = ctypes.create_string_buffer(128)
+        self.lib.rt_dev_last_kernel(buf, len(buf))
+        return buf.value.decode()
+
     def trace_family(self, precision=abi.RT_PREC_F64, traversal=0):
         """The traversal trace_rays takes for the uploaded scene: "FLAT", "LINEAR", "WIDE_LDS", "WIDE_HBM", "STACK"."""
         f = self.lib.rt_trace_family(self.h, precision, traversal)
