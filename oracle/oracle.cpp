@@ -86,6 +86,10 @@ enum { kDimsCamera = 3, kDimsPerBounce = 16, kVolumeSlots = 12 };
 
 struct rngctx {
   int mode = ORC_RNG_COUNTER;
+  uint64_t* ev = nullptr;  // ORC_EV_COUNT event counts of orc_render_events, or none: no draw or value depends on it
+  void count(int e) {
+    if (ev) ev[e]++;
+  }
   uint32_t ks = 0;  // key_path(key_pixel, key_sample)
   uint32_t bounce = 0, jv = 0, js = 0;
   double glibc() const { return std::rand() / (RAND_MAX + 1.0); }  // utility.h:20
@@ -322,6 +326,7 @@ struct hrec {
   v3 p, n;
   double t = 0, u = 0, v = 0;
   bool front = false;
+  uint8_t via = 0;  // event counting only: 1 = met through an instance, 2 = on a moving sphere
   const omat* mat = nullptr;
   void set_face_normal(const ray3& r, const v3& outward) {
     front = dot(r.d, outward) < 0.0;
@@ -372,34 +377,43 @@ struct omat {
       case RT_MAT_LAMBERTIAN:  // material.h:62-67
         s.mode = smode::random;
         s.att = tex->sample(h.u, h.v, h.p);
+        g.count(ORC_EV_TEX + tex->kind);
         s.pdf.kind = pdfsel::cosine;
         make_onb(h.n, s.pdf.onb_x, s.pdf.onb_y, s.pdf.onb_z);
         return true;
       case RT_MAT_METAL: {  // material.h:85-92
         v3 dir = unit(reflect(rin.d, h.n));
         dir = dir + (double)fuzz * random_unit_vec(g);
+        g.count(fuzz == 0 ? ORC_EV_METAL_MIRROR : ORC_EV_METAL_FUZZ);
+        if (dot(dir, h.n) <= 0) g.count(ORC_EV_METAL_BELOW);
         s.mode = smode::determined;
         s.scattered = {h.p, dir, rin.tm};
         s.att = tex->sample(h.u, h.v, h.p);
+        g.count(ORC_EV_TEX + tex->kind);
         return true;
       }
       case RT_MAT_DIELECTRIC: {  // material.h:113-131
         s.mode = smode::determined;
         s.att = tex->sample(h.u, h.v, h.p);
+        g.count(ORC_EV_TEX + tex->kind);
         double ri = h.front ? (1.0 / refr) : (double)refr;
         v3 ud = unit(rin.d);
         double cos_theta = std::fmin(dot(-ud, h.n), 1.0);
         double sin_theta = std::sqrt(1.0 - cos_theta * cos_theta);
         bool cant = ri * sin_theta > 1.0;
-        if (cant || reflectance(cos_theta, ri) > g.scatter())
+        if (cant || reflectance(cos_theta, ri) > g.scatter()) {
           s.scattered = {h.p, reflect(ud, h.n), rin.tm};
-        else
+          g.count(cant ? ORC_EV_DIEL_CANT : ORC_EV_DIEL_SCHLICK);
+        } else {
           s.scattered = {h.p, refract(ud, h.n, ri), rin.tm};
+          g.count(h.front ? ORC_EV_DIEL_REFRACT_FRONT : ORC_EV_DIEL_REFRACT_BACK);
+        }
         return true;
       }
       case RT_MAT_GLOSS: {  // material.h:158-174
         v3 spec_dir = reflect(rin.d, h.n);
         bool specular = g.scatter() <= (double)spec;
+        g.count(specular ? ORC_EV_GLOSS_SPECULAR : ORC_EV_GLOSS_DIFFUSE);
         if (specular) {
           v3 x, y, z;
           make_onb(h.n, x, y, z);
@@ -412,6 +426,7 @@ struct omat {
         } else {
           s.mode = smode::random;
           s.att = tex->sample(h.u, h.v, h.p);
+          g.count(ORC_EV_TEX + tex->kind);
           s.pdf.kind = pdfsel::cosine;
           make_onb(h.n, s.pdf.onb_x, s.pdf.onb_y, s.pdf.onb_z);
         }
@@ -420,6 +435,7 @@ struct omat {
       case RT_MAT_ISOTROPIC:  // material.h:193-198
         s.mode = smode::random;
         s.att = tex->sample(h.u, h.v, h.p);
+        g.count(ORC_EV_TEX + tex->kind);
         s.pdf.kind = pdfsel::sphere;
         return true;
       default:
@@ -513,6 +529,7 @@ struct osphere : ohit {  // sphere.h
     sphere_uv(outward, rec.u, rec.v);
     rec.set_face_normal(r, outward);
     rec.mat = mat;
+    rec.via = moving ? 2 : 0;
     return true;
   }
   box3 bbox() const override { return box; }
@@ -552,6 +569,7 @@ struct oquad : ohit {  // quad.h
     rec.p = hp;
     rec.mat = mat;
     rec.set_face_normal(r, unorm);
+    rec.via = 0;
     return true;
   }
   box3 bbox() const override { return box; }
@@ -595,6 +613,7 @@ struct otri : ohit {  // triangle.h
     rec.u = rec.v = 0;  // the reference leaves u, v stale (triangle.h:27-40); the device uses 0 too
     rec.set_face_normal(r, normal);
     rec.mat = mat;
+    rec.via = 0;
     return true;
   }
   box3 bbox() const override {  // triangle.h:42-48
@@ -671,6 +690,7 @@ struct otranslate : ohit {  // hittable.h:67-89
     ray3 rr{r.o - off, r.d, r.tm};
     if (!obj->hit(rr, t, rec, g)) return false;
     rec.p = rec.p + off;
+    rec.via |= 1;
     return true;
   }
   box3 bbox() const override { return obj->bbox().offset(off); }
@@ -720,6 +740,7 @@ struct orotate : ohit {  // hittable.h:93-293; axis 0 = x, 1 = y, 2 = z
     n[b] = -s * rec.n[a] + c * rec.n[b];
     rec.p = p;
     rec.n = n;
+    rec.via |= 1;
     return true;
   }
   box3 bbox() const override { return box; }
@@ -748,6 +769,7 @@ struct ovolume : ohit {  // volumne.h
     rec.u = rec.v = 0;  // stale in the reference (volumne.h:40-44); 0 here and on the device
     rec.front = true;
     rec.mat = phase;
+    rec.via = 0;
     return true;
   }
   box3 bbox() const override { return boundary->bbox(); }
@@ -844,12 +866,22 @@ struct integrator {
   mutable uint64_t segments = 0;
 
   v3 miss(const ray3& r, rngctx& g) const {  // camera.h:180-190
-    if (!sc->background) return {0, 0, 0};
+    if (!sc->background) {
+      g.count(ORC_EV_MISS_NONE);
+      return {0, 0, 0};
+    }
     osphere s;
     s.center = r.o;
     s.radius = 1.0f;
     hrec rec;
-    if (s.hit(r, ivl(0.001, kInf), rec, g)) return sc->background->sample(rec.u, rec.v, rec.p);
+    if (s.hit(r, ivl(0.001, kInf), rec, g)) {
+      const otex* b = sc->background;
+      const bool black = b->color.x == 0 && b->color.y == 0 && b->color.z == 0;
+      g.count(b->kind != RT_TEX_SOLID ? ORC_EV_MISS_TEXTURED : black ? ORC_EV_MISS_BLACK : ORC_EV_MISS_SOLID);
+      g.count(ORC_EV_TEX + b->kind);
+      return b->sample(rec.u, rec.v, rec.p);
+    }
+    g.count(ORC_EV_MISS_SHORT);
     return {0, 0, 0};
   }
 
@@ -868,13 +900,23 @@ struct integrator {
                    "n=(%.9g %.9g %.9g) front=%d mat=%d\n", max_depth - iteration, r.o.x, r.o.y, r.o.z, r.d.x, r.d.y,
                    r.d.z, rec.t, rec.p.x, rec.p.y, rec.p.z, rec.n.x, rec.n.y, rec.n.z, (int)rec.front, rec.mat->kind);
     v3 emission = rec.mat->emitted(rec);
+    if (g.ev) {
+      if (rec.via & 1) g.count(ORC_EV_INSTANCE);
+      if (rec.via & 2) g.count(ORC_EV_MOVING_SPHERE);
+      if (rec.mat->kind == RT_MAT_DIFFUSE_LIGHT) {
+        g.count(rec.front ? ORC_EV_EMIT_FRONT : ORC_EV_EMIT_BACK);
+        if (rec.front) g.count(ORC_EV_TEX + rec.mat->tex->kind);
+      }
+    }
     srec s;
     if (!rec.mat->scatter(r, rec, s, g)) return emission;
     if (s.mode == smode::determined) {
       v3 in = ray_color(s.scattered, iteration - 1, g);
       return s.att * in + emission;
     }
+    const int mk = rec.mat->kind;
     if (!sc->light) {
+      if (mk != RT_MAT_GLOSS) g.count(mk == RT_MAT_ISOTROPIC ? ORC_EV_ISO_NO_LIGHT : ORC_EV_LAMB_NO_LIGHT);
       ray3 sr{rec.p, pdf_generate(s.pdf, g), r.tm};
       double pv = pdf_value(s.pdf, sr.d);
       double ps = rec.mat->p_scattered(rec, sr);
@@ -884,7 +926,10 @@ struct integrator {
     }
     // dual_pdf(hittable_pdf(light, p), material pdf) (camera.h:228-233, pdf.h:48-61)
     v3 dir;
-    if (g.scatter() < 0.5)
+    const bool light_half = g.scatter() < 0.5;
+    if (mk == RT_MAT_ISOTROPIC) g.count(ORC_EV_ISO_LIGHT);
+    if (mk == RT_MAT_LAMBERTIAN) g.count(light_half ? ORC_EV_LAMB_LIGHT_HALF : ORC_EV_LAMB_COSINE_HALF);
+    if (light_half)
       dir = sc->light->random(rec.p, g);
     else
       dir = pdf_generate(s.pdf, g);
@@ -1241,11 +1286,12 @@ struct job {
   int mode;
 };
 
-inline v3 render_pixel(const job& jb, int x, int y, uint64_t& segs) {  // camera.h:164-170
+inline v3 render_pixel(const job& jb, int x, int y, uint64_t& segs, uint64_t* ev = nullptr) {  // camera.h:164-170
   integrator it{jb.sc, jb.depth};
   v3 sum(0, 0, 0);
   rngctx g;
   g.mode = jb.mode;
+  g.ev = ev;
   uint32_t ka = key_pixel(jb.seed, (uint32_t)(y * jb.W + x));
   for (int k = 0; k < jb.spp; k++) {
     g.ks = key_path(ka, key_sample(jb.seed, (uint32_t)(jb.first + k)));
@@ -1381,6 +1427,14 @@ void orc_scene_free(void* p) { delete static_cast<scene*>(p); }
 int orc_render(const void* scp, const rt_camera_desc* cam, int spp, int first_sample, int max_depth,
                uint64_t seed, int rng_mode, int threads, const rt_tile* tiles, int ntiles, double* out,
                uint64_t* segments) {
+  return orc_render_events(scp, cam, spp, first_sample, max_depth, seed, rng_mode, threads, tiles, ntiles, out,
+                           segments, nullptr, 0);
+}
+
+int orc_render_events(const void* scp, const rt_camera_desc* cam, int spp, int first_sample, int max_depth,
+                      uint64_t seed, int rng_mode, int threads, const rt_tile* tiles, int ntiles, double* out,
+                      uint64_t* segments, uint64_t* events, int nevents) {
+  if (events && nevents < ORC_EV_COUNT) return 1;
   if (!scp || !cam || !tiles || ntiles <= 0 || !out || spp <= 0 || cam->mode < RT_CAM_PERSPECTIVE ||
       cam->mode > RT_CAM_LENS)
     return 1;
@@ -1400,10 +1454,11 @@ int orc_render(const void* scp, const rt_camera_desc* cam, int spp, int first_sa
     for (int y = 0; y < tiles[t].height; y++)
       for (int x = 0; x < tiles[t].width; x++) px.emplace_back(tiles[t].x0 + x, tiles[t].y0 + y);
   uint64_t total_segs = 0;
+  if (events) std::fill(events, events + nevents, (uint64_t)0);
   if (rng_mode == ORC_RNG_COMPAT) {
     if (seed != 0) std::srand((unsigned)seed);
     for (size_t i = 0; i < px.size(); i++) {
-      v3 c = render_pixel(jb, px[i].first, px[i].second, total_segs);
+      v3 c = render_pixel(jb, px[i].first, px[i].second, total_segs, events);
       out[3 * i] = c.x;
       out[3 * i + 1] = c.y;
       out[3 * i + 2] = c.z;
@@ -1412,6 +1467,7 @@ int orc_render(const void* scp, const rt_camera_desc* cam, int spp, int first_sa
     int nt = threads > 0 ? threads : (int)std::max(1u, std::thread::hardware_concurrency());
     std::atomic<size_t> next{0};
     std::vector<uint64_t> segs((size_t)nt, 0);
+    std::vector<uint64_t> evs(events ? (size_t)nt * ORC_EV_COUNT : 0, 0);  // per thread, summed as segs is
     const size_t chunk = 64;
     auto worker = [&](int id) {
       for (;;) {
@@ -1419,7 +1475,8 @@ int orc_render(const void* scp, const rt_camera_desc* cam, int spp, int first_sa
         if (b >= px.size()) break;
         size_t e = std::min(px.size(), b + chunk);
         for (size_t i = b; i < e; i++) {
-          v3 c = render_pixel(jb, px[i].first, px[i].second, segs[(size_t)id]);
+          v3 c = render_pixel(jb, px[i].first, px[i].second, segs[(size_t)id],
+                              events ? evs.data() + (size_t)id * ORC_EV_COUNT : nullptr);
           out[3 * i] = c.x;
           out[3 * i + 1] = c.y;
           out[3 * i + 2] = c.z;
@@ -1431,6 +1488,7 @@ int orc_render(const void* scp, const rt_camera_desc* cam, int spp, int first_sa
     worker(0);
     for (auto& t : pool) t.join();
     for (uint64_t s : segs) total_segs += s;
+    for (size_t i = 0; i < evs.size(); i++) events[i % ORC_EV_COUNT] += evs[i];
   }
   if (segments) *segments = total_segs;
   return 0;

@@ -62,6 +62,44 @@ int orc_render(const void* scene, const rt_camera_desc* cam, int spp, int first_
                uint64_t seed, int rng_mode, int threads, const rt_tile* tiles, int ntiles, double* out,
                uint64_t* segments);
 
+/* The branches of the render path that orc_render_events counts, one count per traced segment that takes the branch
+ * (ORC_EV_TEX + k: a sample of a texture of rt_texture_kind k, by a material, an emitter or the background). */
+enum {
+  ORC_EV_MISS_NONE = 0,       /* a miss with no background */
+  ORC_EV_MISS_BLACK,          /* ... with a solid background (0, 0, 0) */
+  ORC_EV_MISS_SOLID,          /* ... with another solid background */
+  ORC_EV_MISS_TEXTURED,       /* ... with a background of any other texture kind */
+  ORC_EV_MISS_SHORT,          /* a miss under a background whose unit sphere about the origin (camera.h:180-190) the
+                                 ray leaves before t = 0.001, a direction longer than 1000: it returns 0 */
+  ORC_EV_EMIT_FRONT,          /* a diffuse_light met on its front face */
+  ORC_EV_EMIT_BACK,           /* ... on its back face: it emits 0 */
+  ORC_EV_LAMB_LIGHT_HALF,     /* lambertian, the mixture drew the light's direction */
+  ORC_EV_LAMB_COSINE_HALF,    /* lambertian, the mixture drew the cosine direction */
+  ORC_EV_LAMB_NO_LIGHT,       /* lambertian in a scene without a light */
+  ORC_EV_METAL_MIRROR,        /* metal with fuzz 0 */
+  ORC_EV_METAL_FUZZ,          /* metal with fuzz > 0 */
+  ORC_EV_METAL_BELOW,         /* metal whose scattered direction has dot(dir, n) <= 0 */
+  ORC_EV_DIEL_CANT,           /* dielectric reflecting because it cannot refract */
+  ORC_EV_DIEL_SCHLICK,        /* dielectric reflecting by the reflectance draw */
+  ORC_EV_DIEL_REFRACT_FRONT,  /* dielectric refracting at a front face */
+  ORC_EV_DIEL_REFRACT_BACK,   /* dielectric refracting at a back face */
+  ORC_EV_GLOSS_SPECULAR,
+  ORC_EV_GLOSS_DIFFUSE,
+  ORC_EV_ISO_LIGHT,           /* isotropic in a scene with a light */
+  ORC_EV_ISO_NO_LIGHT,
+  ORC_EV_INSTANCE,            /* the segment's hit was met through a translate or rotate */
+  ORC_EV_MOVING_SPHERE,       /* the segment's hit is on a moving sphere */
+  ORC_EV_TEX,                 /* + rt_texture_kind (1..7) */
+  ORC_EV_COUNT = ORC_EV_TEX + 8
+};
+
+/* orc_render, and the counts of the events above over every segment it traced: events[0 .. ORC_EV_COUNT), zeroed
+ * first; nevents is the array's length (>= ORC_EV_COUNT). Counting changes no arithmetic and no random draw: the
+ * image and the segment count are orc_render's, which calls this with events = NULL. */
+int orc_render_events(const void* scene, const rt_camera_desc* cam, int spp, int first_sample, int max_depth,
+                      uint64_t seed, int rng_mode, int threads, const rt_tile* tiles, int ntiles, double* out,
+                      uint64_t* segments, uint64_t* events, int nevents);
+
 /* write_color (color.h:16-36) over a W*H image in render order: P3 text into
  * buf (header included, camera.h:149-151). Returns the byte count needed. */
 size_t orc_write_ppm(const double* image, int width, int height, char* buf, size_t cap);

@@ -35,6 +35,8 @@ def lib():
         L.orc_render.restype = i32
         L.orc_render.argtypes = [vp, P(abi.rt_camera_desc), i32, i32, i32, u64, i32, i32, P(abi.rt_tile), i32, vp,
                                  P(u64)]
+        L.orc_render_events.restype = i32
+        L.orc_render_events.argtypes = L.orc_render.argtypes + [P(u64), i32]
         L.orc_write_ppm.restype = ctypes.c_size_t
         L.orc_write_ppm.argtypes = [vp, i32, i32, ctypes.c_char_p, ctypes.c_size_t]
         L.orc_rng_u32.restype = u32
@@ -101,6 +103,27 @@ def render(scene, cam, spp, max_depth, seed=1, mode=COUNTER, threads=0, tiles=No
         raise RuntimeError("orc_render failed")
     img = out.reshape(cam.image_height, cam.image_width, 3) if full else out
     return img, segs.value
+
+
+# oracle.h's ORC_EV_*: the name of each event count, in order ("tex_<kind>": ORC_EV_TEX + rt_texture_kind)
+EVENTS = ("miss_none", "miss_black", "miss_solid", "miss_textured", "miss_short", "emit_front", "emit_back",
+          "lamb_light_half", "lamb_cosine_half", "lamb_no_light", "metal_mirror", "metal_fuzz", "metal_below",
+          "diel_cant", "diel_schlick", "diel_refract_front", "diel_refract_back", "gloss_specular", "gloss_diffuse",
+          "iso_light", "iso_no_light", "instance", "moving_sphere", "tex_0", "tex_solid", "tex_checker", "tex_perlin",
+          "tex_value", "tex_worley", "tex_voronoi", "tex_image")
+
+
+def render_events(scene, cam, spp, max_depth, seed=1, mode=COUNTER, threads=0):
+    """render() of the whole frame, and the event counts of its segments: (image, segments, {event name: count})."""
+    tile = (abi.rt_tile * 1)(abi.rt_tile(0, 0, cam.image_width, cam.image_height))
+    out = np.zeros((cam.image_width * cam.image_height, 3), dtype=np.float64)
+    segs = ctypes.c_uint64()
+    ev = (ctypes.c_uint64 * len(EVENTS))()
+    rc = lib().orc_render_events(scene.h, ctypes.byref(cam), spp, 0, max_depth, seed, mode, threads, tile, 1,
+                                 out.ctypes.data, ctypes.byref(segs), ev, len(EVENTS))
+    if rc != 0:
+        raise RuntimeError("orc_render_events failed")
+    return out.reshape(cam.image_height, cam.image_width, 3), segs.value, dict(zip(EVENTS, ev))
 
 
 def ppm(image):
