@@ -909,7 +909,7 @@ struct TravDefaults {
   struct Tables {};
   static constexpr int kStack = 0;           // the binary BVH's LDS stack entries per lane
   static constexpr int kLdsNodes = 0;        // the binary BVH's nodes copied into LDS, at most
-  static constexpr uint32_t kLdsMats = 16;   // materials the LL kernels' LDS table holds
+  static constexpr uint32_t kLdsMats = kLdsMatsLL;  // materials the LL kernels' LDS table holds (rt_plan.h)
   // the scene class shade is compiled for (ShadeOf): lambertian + light, no light, LL + isotropic; moving spheres
   [[maybe_unused]] static constexpr bool kLL = false, kNL = false, kLLI = false, kMoving = true;
   // the path state (Path): lean, no radiance register, cold fields in LDS, throughput in LDS
@@ -977,8 +977,10 @@ struct FlatTrav : TravDefaults {
   // ~27 KB with the general sizes -- leaves room for 6 blocks per CU)
   // (the fp64 LL kernel's 7 blocks per CU leave no whole 512-byte LDS granule: its one room record, 112 B, takes
   // the place of two of its 16 quad slots, 128 B -- a room stands for five or six quads)
-  static constexpr uint32_t kLdsQuads = LL ? 14 : 64, kLdsBoxes = LL ? 8 : 16, kLdsMats = LL ? 16 : 32;
-  static constexpr uint32_t kLdsRooms = LL ? 1 : 2;
+  // The sizes are rt_plan.h's (kFlatLds, kFlatLdsLL): path_kernel gives this kernel only to a scene they hold.
+  static constexpr FlatCaps kCaps = LL ? kFlatLdsLL : kFlatLds;
+  static constexpr uint32_t kLdsQuads = kCaps.quads, kLdsBoxes = kCaps.boxes, kLdsMats = kCaps.mats;
+  static constexpr uint32_t kLdsRooms = kCaps.rooms;
   struct Tables {
     FlatQuadT<R> q[kLdsQuads];
     FlatRoomT<R> r[kLdsRooms];
@@ -986,10 +988,6 @@ struct FlatTrav : TravDefaults {
     Material<R> m[LL ? 1 : kLdsMats];
     R4<R> lm[LL ? kLdsMats : 1];  // LL: (solid colour, 1 for diffuse_light)
   };
-  __host__ __device__ __forceinline__ static bool tables_fit(const DevScene<R>& sc) {
-    return sc.n_flatq[0] + sc.n_flatq[1] + sc.n_flatq[2] <= kLdsQuads && sc.n_flatb <= kLdsBoxes &&
-           sc.n_flatr <= kLdsRooms && sc.n_mats <= kLdsMats;
-  }
   __device__ __forceinline__ static void fill(const DevScene<R>& sc, Tables& tb) {
     const uint32_t nq = sc.n_flatq[0] + sc.n_flatq[1] + sc.n_flatq[2];
     for (uint32_t j = threadIdx.x; j < nq; j += kBlock) tb.q[j] = sc.flatq[j];
@@ -1011,9 +1009,8 @@ struct FlatTrav : TravDefaults {
     trace_flat<R, sizeof(R) == 8>(sc, s.o, s.d, s.xe, s.xi, t, e, i, nm, tb.q, tb.r, tb.b);
   }
 };
-// LDSN: the scene's BVH nodes (at most kLdsNodeMax) are copied into LDS at kernel start, so
+// LDSN: the scene's BVH nodes (at most kLdsNodeMax, rt_plan.h) are copied into LDS at kernel start, so
 // every traversal step reads LDS instead of waiting on the memory hierarchy (RTOW: 117 nodes)
-constexpr uint32_t kLdsNodeMax = 256;
 template <class R, int STACK, bool LDSN = false>
 struct StackTrav : TravDefaults {  // (no cold state in LDS: its LDS holds the traversal stacks)
   static constexpr bool kClosestOccl = true;  // (fp32 rays re-decide near-edge quad hits in fp64: occlusion_early_exit)
@@ -1285,7 +1282,7 @@ __device__ __forceinline__ void persist_body(const Params<R>& p) {
   const Material<R>* mats = nullptr;
   const R4<R>* lm = nullptr;
   [[maybe_unused]] const typename Trav::Tables* flat_tb = nullptr;
-  if constexpr (Trav::kTablesLds) {  // the host launches this kernel only when the tables fit
+  if constexpr (Trav::kTablesLds) {  // path_kernel (rt_plan.h) gives this kernel only to a scene whose tables fit
     __shared__ typename Trav::Tables tb;
     Trav::fill(p.sc, tb);
     __syncthreads();
@@ -2016,7 +2013,8 @@ thread_local uint64_t t_grid_lanes = 0;
 
 // The tag of a path kernel (rt_dev_last_kernel): its traversal policy with every template argument in order (the
 // precision first, as f32 / f64; bools as 0 / 1), "camx" for the extended camera and texture form, and the schedule:
-// "WideTrav<f64,0,1,1,0,1,1,0> persist", "LinearTrav<f32,1,1,1,0> camx step". Host code only.
+// "WideTrav<f64,0,1,1,0,1,1,0> persist", "LinearTrav<f32,1,1,1,0> camx step". Host code only. Built from the
+// instantiated types, not from the plan: it is the evidence of what ran (rt_plan.h path_kernel_tag spells the plan's).
 template <class R, class... A>
 std::string trav_tag(const char* name, A... args) {
   std::string s = std::string(name) + (sizeof(R) == 8 ? "<f64" : "<f32");
@@ -2095,51 +2093,36 @@ inline size_t wide_lds_bytes(const DevScene<R>& sc, bool ldsn) {
   if (ldsn) return wide_lds_tree_bytes(sc.n_wnodes, sc.n_wprim_words, sc.wide_stack, sizeof(typename WWord<R>::T));
   return stack + top;
 }
+// A launch over a wide tree in HBM whose stack spills: the spill area holds spill_lanes lanes, never launch more
+// (the resident grid is below it)
+template <class R>
+uint32_t spill_grid(const DevScene<R>& sc, uint32_t grid) {
+  return sc.wide_spill ? std::min<uint32_t>(grid, sc.spill_lanes / kBlock) : grid;
+}
+// The wide kernel of the plan's primitive kinds and shade class, over a tree in LDS or in HBM
 template <class R, bool SPH, bool TRI, bool QUAD, bool MOV, bool LL = false, bool NL = false>
-void launch_wide_k(const Params<R>& p, uint32_t grid, hipStream_t st) {
-  const size_t full = wide_lds_bytes(p.sc, true);
-  const uint32_t spill_grid = p.sc.wide_spill ? std::min<uint32_t>(grid, p.sc.spill_lanes / kBlock) : grid;
-  if (wide_tree_in_lds(p.sc.n_wnodes, p.sc.n_wprim_words, p.sc.wide_stack, sizeof(typename WWord<R>::T))) {
+void launch_wide_k(const Params<R>& p, const PathKernel& k, uint32_t grid, hipStream_t st) {
+  if (k.lds) {
     using InLds = WideTrav<R, SPH, TRI, QUAD, MOV, true, LL, NL>;
-    launch_one<InLds, false>(k_persist_occ<R, InLds, false>, p, grid, st, full);
+    launch_one<InLds, false>(k_persist_occ<R, InLds, false>, p, grid, st, wide_lds_bytes(p.sc, true));
     return;
   }
-  // the spill area holds spill_lanes lanes: never launch more (the resident grid is below it)
   using InHbm = WideTrav<R, SPH, TRI, QUAD, MOV, false, LL, NL>;
-  launch_one<InHbm, false>(k_persist_occ<R, InHbm, false>, p, spill_grid, st, wide_lds_bytes(p.sc, false));
+  launch_one<InHbm, false>(k_persist_occ<R, InHbm, false>, p, spill_grid(p.sc, grid), st, wide_lds_bytes(p.sc, false));
 }
-// Kernel for the primitive kinds of the scene: spheres only (RTOW), triangles only or triangles and
-// quads (meshes, the C4 stand-in with its light), or all.
-template <class R>
-inline void launch_wide(const Params<R>& p, bool ll, bool nl, uint32_t grid, hipStream_t st) {
-  const uint32_t k = p.sc.wide_kinds;
-  if (k == WK_SPHERE && nl)  // RTOW (C3)
-    launch_wide_k<R, true, false, false, false, false, true>(p, grid, st);
-  else if (k == WK_SPHERE)
-    launch_wide_k<R, true, false, false, false>(p, grid, st);
-  else if (k == WK_TRI)
-    launch_wide_k<R, false, true, false, false>(p, grid, st);
-  else if (k == (WK_TRI | WK_QUAD) && ll && p.sc.n_mats <= 16)
-    launch_wide_k<R, false, true, true, false, true>(p, grid, st);  // ... lambertian + light (the C4 stand-in)
-  else if (k == (WK_TRI | WK_QUAD))  // a mesh under a quad light
-    launch_wide_k<R, false, true, true, false>(p, grid, st);
-  else
-    launch_wide_k<R, true, true, true, true>(p, grid, st);
-}
+// A flat, linear or binary-BVH kernel in the plan's form (base or extended) and schedule
 template <class R, class Trav>
-void launch_k(const Params<R>& p, uint32_t grid, hipStream_t st) {
-  const bool camx = p.cam_mode != RT_CAM_PERSPECTIVE || p.sc.has_procedural;
-  // the flat program only runs perspective renders without procedural textures (kernel_family): no CAMX form
-  if (camx && !Trav::kFlat) {
+void launch_k(const Params<R>& p, const PathKernel& k, uint32_t grid, hipStream_t st) {
+  if (k.camx) {  // (the flat program has no CAMX form: path_kernel)
     if constexpr (!Trav::kFlat) {
-      if (p.persist)
+      if (k.persist)
         launch_one<Trav, true>(k_persist_occ<R, Trav, true>, p, grid, st);
       else
         launch_one<Trav, true>(k_step_occ<R, Trav, true>, p, grid, st);
     }
     return;
   }
-  if (p.persist) {
+  if (k.persist) {
     if constexpr (Trav::kWaves > 1)
       launch_one<Trav, false>(k_persist_occ<R, Trav, false>, p, grid, st);
     else
@@ -2188,10 +2171,8 @@ void with_query_family(const DevScene<R>& sc, TraceFamily fam, F&& f) {
         f(TravTag<WideTrav<R, true, true, true, true, true>>{}, kMaxBlocks, wide_lds_bytes(sc, true));
       return;
     case TF_WIDE_HBM:
-      if constexpr (family_built(KF_WIDE))  // the spill area holds spill_lanes lanes: never launch more
-        f(TravTag<WideTrav<R, true, true, true, true, false>>{},
-          sc.wide_spill ? std::min<uint32_t>(kMaxBlocks, sc.spill_lanes / kBlock) : kMaxBlocks,
-          wide_lds_bytes(sc, false));
+      if constexpr (family_built(KF_WIDE))
+        f(TravTag<WideTrav<R, true, true, true, true, false>>{}, spill_grid(sc, kMaxBlocks), wide_lds_bytes(sc, false));
       return;
     case TF_STACK:
       if constexpr (family_built(KF_STACK)) f(TravTag<StackTrav<R, kStackDepth>>{}, kMaxBlocks, kNoLds);
@@ -2204,60 +2185,69 @@ void with_query_family(const DevScene<R>& sc, TraceFamily fam, F&& f) {
 // ====================================================================== rt_launch.h
 namespace rtd {
 
+// The instantiation a PathKernel names, one line per policy. Nothing is decided here: which scene gets which kernel is
+// path_kernel's (rt_plan.h), and the tag reported afterwards is the instantiated type's (launch_one).
 template <class R>
-void launch_step(const LaunchParams<R>& lp, KernelFamily fam, bool ll, bool nl, bool lli, int stack, uint32_t grid,
-                 hipStream_t st) {
+void launch_step(const LaunchParams<R>& lp, const PathKernel& k, uint32_t grid, hipStream_t st) {
   const Params<R> p{lp};
-  switch (fam) {
+  switch (k.fam) {
     case KF_FLAT:
       if constexpr (family_built(KF_FLAT)) {
-        if (p.persist && FlatTrav<R, true>::tables_fit(p.sc)) {
-          if (ll && FlatTrav<R, true, true>::tables_fit(p.sc))
-            launch_k<R, FlatTrav<R, true, true>>(p, grid, st);
-          else
-            launch_k<R, FlatTrav<R, true>>(p, grid, st);
-        } else {
-          launch_k<R, FlatTrav<R>>(p, grid, st);
-        }
+        if (k.shade == SH_LL)
+          launch_k<R, FlatTrav<R, true, true>>(p, k, grid, st);
+        else if (k.lds)
+          launch_k<R, FlatTrav<R, true>>(p, k, grid, st);
+        else
+          launch_k<R, FlatTrav<R>>(p, k, grid, st);
       }
       return;
     case KF_LIN_QUAD:
-      if constexpr (family_built(KF_LIN_QUAD)) launch_k<R, LinearTrav<R, false, false, false>>(p, grid, st);
+      if constexpr (family_built(KF_LIN_QUAD)) launch_k<R, LinearTrav<R, false, false, false>>(p, k, grid, st);
       return;
     case KF_LIN_VOL:
       if constexpr (family_built(KF_LIN_VOL)) {
-        // lambertian + isotropic + light (C5), persistent schedule only: the LLI form's shade and LDS material table
-        // are persist_body's; step_body (segments_per_launch > 0) shades with the general program, which its
-        // register budget would squeeze
-        if (lli && p.persist && p.sc.n_mats <= 16)
-          launch_k<R, LinearTrav<R, false, false, true, true>>(p, grid, st);
+        if (k.shade == SH_LLI)
+          launch_k<R, LinearTrav<R, false, false, true, true>>(p, k, grid, st);
         else
-          launch_k<R, LinearTrav<R, false, false, true>>(p, grid, st);
+          launch_k<R, LinearTrav<R, false, false, true>>(p, k, grid, st);
       }
       return;
     case KF_LIN_SPH:
-      if constexpr (family_built(KF_LIN_SPH)) launch_k<R, LinearTrav<R, true, false, false>>(p, grid, st);
+      if constexpr (family_built(KF_LIN_SPH)) launch_k<R, LinearTrav<R, true, false, false>>(p, k, grid, st);
       return;
     case KF_LIN_ALL:
-      if constexpr (family_built(KF_LIN_ALL)) launch_k<R, LinearTrav<R, true, true, true>>(p, grid, st);
+      if constexpr (family_built(KF_LIN_ALL)) launch_k<R, LinearTrav<R, true, true, true>>(p, k, grid, st);
       return;
     case KF_WIDE:
-      if constexpr (family_built(KF_WIDE)) launch_wide(p, ll, nl, grid, st);
+      if constexpr (family_built(KF_WIDE)) {
+        if (k.kinds == WK_SPHERE && k.shade == SH_NL)
+          launch_wide_k<R, true, false, false, false, false, true>(p, k, grid, st);
+        else if (k.kinds == WK_SPHERE)
+          launch_wide_k<R, true, false, false, false>(p, k, grid, st);
+        else if (k.kinds == WK_TRI)
+          launch_wide_k<R, false, true, false, false>(p, k, grid, st);
+        else if (k.kinds == (WK_TRI | WK_QUAD) && k.shade == SH_LL)
+          launch_wide_k<R, false, true, true, false, true>(p, k, grid, st);
+        else if (k.kinds == (WK_TRI | WK_QUAD))
+          launch_wide_k<R, false, true, true, false>(p, k, grid, st);
+        else
+          launch_wide_k<R, true, true, true, true>(p, k, grid, st);
+      }
       return;
     case KF_STACK:
       if constexpr (family_built(KF_STACK)) {
         if constexpr (sizeof(R) == 4) {  // nodes in LDS: fp32 only
-          if (p.sc.n_nodes <= kLdsNodeMax && stack <= 16) {
-            launch_k<R, StackTrav<R, 16, true>>(p, grid, st);
+          if (k.lds) {
+            launch_k<R, StackTrav<R, kStackMid, true>>(p, k, grid, st);
             return;
           }
         }
-        if (stack <= 8)
-          launch_k<R, StackTrav<R, 8>>(p, grid, st);
-        else if (stack <= 16)
-          launch_k<R, StackTrav<R, 16>>(p, grid, st);
+        if (k.stack == kStackSmall)
+          launch_k<R, StackTrav<R, kStackSmall>>(p, k, grid, st);
+        else if (k.stack == kStackMid)
+          launch_k<R, StackTrav<R, kStackMid>>(p, k, grid, st);
         else
-          launch_k<R, StackTrav<R, kStackDepth>>(p, grid, st);
+          launch_k<R, StackTrav<R, kStackDepth>>(p, k, grid, st);
       }
       return;
   }
@@ -2307,9 +2297,9 @@ void launch_camera_rays(const CamRayParams& p, hipStream_t st) {
 }
 
 template <class R>
-void launch_init(const LaunchParams<R>& lp, uint32_t blocks, hipStream_t st) {
+void launch_init(const LaunchParams<R>& lp, const PathKernel& k, uint32_t blocks, hipStream_t st) {
   const Params<R> p{lp};
-  if (p.cam_mode != RT_CAM_PERSPECTIVE || p.sc.has_procedural)
+  if (k.camx)
     hipLaunchKernelGGL((k_init<R, true>), dim3(blocks), dim3(kBlock), 0, st, p);
   else
     hipLaunchKernelGGL((k_init<R, false>), dim3(blocks), dim3(kBlock), 0, st, p);
@@ -2340,8 +2330,8 @@ void launch_pixmap(const uint4* tiles, uint32_t ntiles, uint32_t npix, uint32_t*
 
 #define RT_INSTANTIATE(R)                                                                                        \
   template void launch_zero<R>(R*, uint64_t, hipStream_t);                                                       \
-  template void launch_step<R>(const LaunchParams<R>&, KernelFamily, bool, bool, bool, int, uint32_t, hipStream_t); \
-  template void launch_init<R>(const LaunchParams<R>&, uint32_t, hipStream_t);                                   \
+  template void launch_step<R>(const LaunchParams<R>&, const PathKernel&, uint32_t, hipStream_t);                \
+  template void launch_init<R>(const LaunchParams<R>&, const PathKernel&, uint32_t, hipStream_t);                \
   template void launch_trace<R>(const TraceParams<R>&, TraceFamily, hipStream_t);                                \
   template void launch_aov<R>(const AovParams<R>&, TraceFamily, hipStream_t);                                    \
   template void launch_occluded<R>(const OcclParams<R>&, TraceFamily, bool, hipStream_t);                        \

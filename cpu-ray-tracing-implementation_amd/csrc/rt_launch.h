@@ -90,18 +90,17 @@ constexpr bool family_built(KernelFamily f) {
 #define RT_WIDE_WAVES_GLOBAL 8  // round 5, with 12 LDS stack entries and 55 top nodes in LDS (wide_lds_stack)
 #endif
 
-// One launch of the render's path kernel (k_persist* or k_step* of the family): `grid` blocks at most (the
-// persistent schedule cuts it to the resident blocks). ll / nl / lli: the scene-class predicates of
-// rt_plan.h; stack: the binary BVH's stack need. Defined for float and double.
+// One launch of the render's path kernel, the one `k` names (rt_plan.h path_kernel, of the header and the precision
+// p.sc was made from): `grid` blocks at most (the persistent schedule cuts it to the resident blocks, a spilling wide
+// tree to its spill area). Defined for float and double.
 template <class R>
-void launch_step(const LaunchParams<R>& p, KernelFamily fam, bool ll, bool nl, bool lli, int stack, uint32_t grid,
-                 hipStream_t st);
+void launch_step(const LaunchParams<R>& p, const PathKernel& k, uint32_t grid, hipStream_t st);
 uint64_t last_grid_lanes();  // lanes of the last persistent launch_step on this host thread
 const char* last_kernel();   // tag of the kernel the last launch_step on this host thread launched ("" before the first)
 
-// wavefront schedule: the first camera ray of every slot; live-slot count and compaction
+// wavefront schedule: the first camera ray of every slot (in k's form, base or extended); live-slot count and compaction
 template <class R>
-void launch_init(const LaunchParams<R>& p, uint32_t blocks, hipStream_t st);
+void launch_init(const LaunchParams<R>& p, const PathKernel& k, uint32_t blocks, hipStream_t st);
 void launch_count(const void* D, int f64, const uint32_t* queue, uint32_t n, uint32_t* blk, uint32_t* total,
                   hipStream_t st);  // k_count + k_scan: blk = exclusive block offsets, *total = live slots
 void launch_compact(const void* D, int f64, const uint32_t* queue, uint32_t n, const uint32_t* blk_off, uint32_t* out,

@@ -1,6 +1,6 @@
 // rt_plan.h -- the host's decisions about a render, as pure functions of the compiled scene's header and the
-// call's sizes: which kernel family it takes (and which traversal a ray query takes, whether a wide tree lives in
-// LDS), and how its samples are cut into work items and passes. No
+// call's sizes: which kernel family it takes and which path kernel of that family (path_kernel; which traversal a ray
+// query takes, whether a wide tree lives in LDS), and how its samples are cut into work items and passes. No
 // HIP and no environment access, so the decisions are testable without a GPU (tests/test_plan.py).
 #pragma once
 
@@ -8,6 +8,8 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <initializer_list>
+#include <string>
 
 #include "../../include/rt_hip.h"
 #include "rt_scene.h"
@@ -24,27 +26,34 @@ inline void div_magic(uint32_t d, uint64_t& m, uint32_t& k) {
   m = (uint64_t)((((unsigned __int128)1) << k) / d) + 1;
 }
 
+// Whether a render needs its kernels' extended form (CAMX: k_init, the linear program's and the binary BVH's path
+// kernels): a camera model other than the perspective one, or a procedural or picture texture. The flat program and
+// the wide tree have no such form: kernel_family keeps an extended render off them.
+inline bool extended_form(const SceneHeader& h, int32_t cam_mode) {
+  return cam_mode != RT_CAM_PERSPECTIVE || h.n_texdata > 0 || h.has_cell_noise;
+}
+
 // The kernel family a render takes, decided from the compiled scene, the camera model, the schedule and the
-// traversal order (launch_step launches it).
+// traversal order (path_kernel chooses the kernel within it).
 enum KernelFamily { KF_FLAT, KF_LIN_QUAD, KF_LIN_VOL, KF_LIN_SPH, KF_LIN_ALL, KF_WIDE, KF_STACK };
 inline KernelFamily kernel_family(const SceneHeader& h, int32_t cam_mode, bool persist, bool ordered) {
-  const bool persp = cam_mode == RT_CAM_PERSPECTIVE, procedural = h.n_texdata > 0 || h.has_cell_noise;
+  const bool ext = extended_form(h, cam_mode);
   const bool sph = h.n_spheres > 0, tri = h.n_tris > 0, vol = h.has_volumes != 0;
   // the flat program (world-space quads and boxes, fp32 and fp64); the extended kernels keep the linear one
-  if (!ordered && h.has_flat && persp && !procedural) return KF_FLAT;
+  if (!ordered && h.has_flat && !ext) return KF_FLAT;
   if (h.n_linear > 0) {
     if (!sph && !tri) return vol ? KF_LIN_VOL : KF_LIN_QUAD;
     return (sph && !tri && !vol) ? KF_LIN_SPH : KF_LIN_ALL;
   }
   // the wide BVH (persistent schedule, base kernels; fp64 rays since round 3)
-  if (!ordered && h.has_wide && persist && persp && !procedural) return KF_WIDE;
+  if (!ordered && h.has_wide && persist && !ext) return KF_WIDE;
   return KF_STACK;
 }
 // Lanes of a block of every path and query kernel (the LDS sizes below count per-lane stack entries by it).
 constexpr int kBlock = 256;
 
 // Whether a wide-BVH launch keeps the whole tree in the block's LDS (else: the tree in HBM, the stack and the top
-// of the tree in LDS). The one home of that decision: launch_wide_k, launch_trace and trace_family ask here.
+// of the tree in LDS). The one home of that decision: path_kernel and trace_family ask here.
 // word_bytes: a primitive word of the blob the rays read, 16 (fp32) or 32 (fp64).
 constexpr size_t kWideLdsBudget = 40u << 10;  // bytes per 256-lane block: 4 blocks per CU of 160 KiB
 inline size_t wide_lds_tree_bytes(uint32_t n_wnodes, uint32_t n_wprim_words, uint32_t wide_stack, size_t word_bytes) {
@@ -131,6 +140,100 @@ inline bool lamb_iso_light_scene(const SceneHeader& h) {
   const uint32_t ok_m = (1u << M_LAMBERTIAN) | (1u << M_DIFFUSE_LIGHT) | (1u << M_ISOTROPIC);
   return (h.mat_kinds & ~ok_m) == 0 && (h.tex_kinds & ~(1u << T_SOLID)) == 0 && h.light_kind == L_QUAD &&
          h.light_aligned != 0;
+}
+
+// ------------------------------------------------------------------ the path kernel
+// What the kernels keep in fixed-size LDS tables, and so what a scene may have at most to be given such a kernel:
+// the policies (rt_kernels.hip) size their tables by these names and path_kernel tests a scene against them.
+// The flat program's records and materials (FlatTrav::Tables), in its general and its LL form:
+struct FlatCaps {
+  uint32_t quads, boxes, rooms, mats;
+};
+constexpr FlatCaps kFlatLds{64, 16, 2, 32}, kFlatLdsLL{14, 8, 1, 16};
+inline bool flat_tables_fit(const SceneHeader& h, const FlatCaps& c) {
+  return h.n_flat_quad[0] + h.n_flat_quad[1] + h.n_flat_quad[2] <= c.quads && h.n_flat_box <= c.boxes &&
+         h.n_flat_room <= c.rooms && h.n_mats <= c.mats;
+}
+constexpr uint32_t kLdsNodeMax = 256;  // the binary BVH's nodes in LDS (StackTrav LDSN, fp32 only)
+constexpr uint32_t kLdsMatsLL = 16;    // materials of the linear LLI and wide LL kernels' LDS table (wlm_tab)
+constexpr int kStackSmall = 8, kStackMid = 16;  // the binary BVH's LDS stacks below kStackDepth entries
+
+// One path kernel by name: what launch_step instantiates and path_kernel_tag spells.
+enum ShadeClass { SH_GENERAL, SH_LL, SH_NL, SH_LLI };  // lamb_light_scene, no_light_scene, lamb_iso_light_scene
+struct PathKernel {
+  KernelFamily fam;
+  ShadeClass shade;
+  bool lds;        // in LDS: the flat program's tables, the binary BVH's nodes, the wide tree
+  int stack;       // binary BVH: the LDS stack entries of a lane, kStackSmall, kStackMid or kStackDepth; else 0
+  uint32_t kinds;  // wide tree: the WK_* primitive kinds the kernel tests, one of six sets; else 0
+  bool camx;       // the extended form (the linear program and the binary BVH alone)
+  bool persist;    // the persistent schedule, else the wavefront schedule
+};
+// The path kernel a render launches. h: the header of the blob the precision reads (hdr or hdr64: an fp64 flat scene
+// stores a room's walls as one room record, so the two can fall on different sides of the flat tables' limits);
+// word_bytes: a primitive word of that blob, 16 (fp32) or 32 (fp64); stack_need: CompiledScene::stack_need.
+inline PathKernel path_kernel(const SceneHeader& h, size_t word_bytes, int32_t cam_mode, bool persist, bool ordered,
+                              int stack_need) {
+  PathKernel k{};
+  k.fam = kernel_family(h, cam_mode, persist, ordered);
+  k.shade = SH_GENERAL;
+  k.persist = persist;
+  // (the flat program and the wide tree never see an extended render: kernel_family)
+  k.camx = k.fam != KF_FLAT && k.fam != KF_WIDE && extended_form(h, cam_mode);
+  const bool few_mats = h.n_mats <= kLdsMatsLL;
+  switch (k.fam) {
+    case KF_FLAT:
+      // the tables in LDS: the persistent kernel alone; the LL form's tables are smaller
+      k.lds = persist && flat_tables_fit(h, kFlatLds);
+      if (k.lds && lamb_light_scene(h) && flat_tables_fit(h, kFlatLdsLL)) k.shade = SH_LL;
+      break;
+    case KF_LIN_VOL:
+      // lambertian + isotropic + light (C5), persistent schedule only: the LLI form's shade and LDS material table
+      // are persist_body's; step_body (segments_per_launch > 0) shades with the general program, which its
+      // register budget would squeeze
+      if (lamb_iso_light_scene(h) && persist && few_mats) k.shade = SH_LLI;
+      break;
+    case KF_WIDE:
+      // the primitive kinds of the scene: spheres only (RTOW, C3: NL), triangles only, triangles and quads (a mesh
+      // under a quad light; lambertian + light, the C4 stand-in: LL), or all, moving spheres among them
+      k.kinds = (h.wide_kinds == WK_SPHERE || h.wide_kinds == WK_TRI || h.wide_kinds == (WK_TRI | WK_QUAD))
+                    ? h.wide_kinds
+                    : (WK_SPHERE | WK_TRI | WK_QUAD | WK_MOVING);
+      if (k.kinds == WK_SPHERE && no_light_scene(h)) k.shade = SH_NL;
+      if (k.kinds == (WK_TRI | WK_QUAD) && lamb_light_scene(h) && few_mats) k.shade = SH_LL;
+      k.lds = wide_tree_in_lds(h.n_wnodes, h.n_wprim_words, h.wide_stack, word_bytes);
+      break;
+    case KF_STACK:
+      k.lds = word_bytes == 16 && h.n_nodes <= kLdsNodeMax && stack_need <= kStackMid;  // nodes in LDS: fp32 only
+      k.stack = stack_need <= kStackSmall ? kStackSmall : stack_need <= kStackMid ? kStackMid : kStackDepth;
+      if (k.lds) k.stack = kStackMid;  // (the one kernel with its nodes in LDS)
+      break;
+    default:  // the other linear programs: one kernel each
+      break;
+  }
+  return k;
+}
+// The kernel's tag as rt_dev_last_kernel reports it (rt_kernels.hip kernel_tag): the traversal policy with every
+// template argument in order (the precision first, bools as 0 / 1), "camx" for the extended form, and the schedule:
+// "WideTrav<f64,0,1,1,0,1,1,0> persist", "LinearTrav<f32,1,1,1,0> camx step".
+inline std::string path_kernel_tag(const PathKernel& k, size_t word_bytes) {
+  auto trav = [&](const char* name, std::initializer_list<int> args) {
+    std::string s = std::string(name) + (word_bytes == 32 ? "<f64" : "<f32");
+    for (int a : args) s += "," + std::to_string(a);
+    return s + ">" + (k.camx ? " camx" : "") + (k.persist ? " persist" : " step");
+  };
+  const bool sph = k.fam == KF_LIN_SPH || k.fam == KF_LIN_ALL, all = k.fam == KF_LIN_ALL;
+  switch (k.fam) {
+    case KF_FLAT:
+      return trav("FlatTrav", {k.lds, k.shade == SH_LL});
+    case KF_WIDE:
+      return trav("WideTrav", {(k.kinds & WK_SPHERE) != 0, (k.kinds & WK_TRI) != 0, (k.kinds & WK_QUAD) != 0,
+                               (k.kinds & WK_MOVING) != 0, k.lds, k.shade == SH_LL, k.shade == SH_NL});
+    case KF_STACK:
+      return trav("StackTrav", {k.stack, k.lds});
+    default:  // SPH, TRI, VOL, LLI
+      return trav("LinearTrav", {sph, all, all || k.fam == KF_LIN_VOL, k.shade == SH_LLI});
+  }
 }
 
 // ------------------------------------------------------------------ the item layout

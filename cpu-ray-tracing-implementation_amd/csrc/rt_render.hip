@@ -247,7 +247,7 @@ DevScene<R> dev_scene(const SceneHeader& h, void* base) {
   s.n_nodes = h.n_nodes;
   s.texdata = (const double*)at(h.off_texdata);
   s.images = (const uint8_t*)at(h.off_images);
-  s.has_procedural = h.n_texdata > 0 || h.has_cell_noise;
+  s.has_procedural = extended_form(h, RT_CAM_PERSPECTIVE);  // (by its textures alone)
   s.has_wide = (int32_t)h.has_wide;
   s.wnodes = (const WNode*)at(h.off_wnodes);
   s.wprims = (const typename WWord<R>::T*)at(h.off_wprims);
@@ -314,16 +314,9 @@ bool env_frame_overlap() {
   return !(v && *v) || std::strtol(v, nullptr, 10) != 0;
 }
 
-// What launch_step needs besides the parameters
-struct StepKind {
-  KernelFamily fam;
-  bool ll, nl, lli;
-  int stack;
-};
-
 // One launch_step, between two events when the context collects kernel times (settle() sums the pairs)
 template <class R>
-rt_status timed_step(rt_context* c, const LaunchParams<R>& p, const StepKind& k, uint32_t grid, hipStream_t st,
+rt_status timed_step(rt_context* c, const LaunchParams<R>& p, const PathKernel& k, uint32_t grid, hipStream_t st,
                      bool on_lane = false) {
   hipEvent_t e0 = nullptr, e1 = nullptr;
   if (c->timing) {
@@ -332,7 +325,7 @@ rt_status timed_step(rt_context* c, const LaunchParams<R>& p, const StepKind& k,
     if (!e0 || !e1) return set_err(c, RT_ERR_HIP, "hipEventCreate failed");
     RT_HIP(c, hipEventRecord(e0, st));
   }
-  launch_step<R>(p, k.fam, k.ll, k.nl, k.lli, k.stack, grid, st);
+  launch_step<R>(p, k, grid, st);
   if (c->timing) {
     RT_HIP(c, hipEventRecord(e1, st));
     c->ev_lane.resize(c->ev_used / 2 + 1, 0);
@@ -347,7 +340,7 @@ rt_status timed_step(rt_context* c, const LaunchParams<R>& p, const StepKind& k,
 // The persistent schedule (the default): one launch of at most `grid` blocks renders the pass. A fault is
 // reported by the settle after the call (rt_stats, or a host-output render).
 template <class R>
-rt_status run_persistent(rt_context* c, const LaunchParams<R>& p, const StepKind& k, uint32_t grid, hipStream_t st,
+rt_status run_persistent(rt_context* c, const LaunchParams<R>& p, const PathKernel& k, uint32_t grid, hipStream_t st,
                          bool on_lane = false) {
   RT_HIP(c, hipMemsetAsync(p.heads, 0, 4ull * kHeads * kHeadStride, st));
   rt_status s;
@@ -360,11 +353,11 @@ rt_status run_persistent(rt_context* c, const LaunchParams<R>& p, const StepKind
 // The wavefront schedule (segments_per_launch = K > 0): P slots with their path state in HBM, one launch per K
 // segments, the live slots counted every kBatch launches and compacted into a queue once half have finished.
 template <class R>
-rt_status run_wavefront(rt_context* c, LaunchParams<R> p, const StepKind& k, uint32_t nblk_max, hipStream_t st) {
+rt_status run_wavefront(rt_context* c, LaunchParams<R> p, const PathKernel& k, uint32_t nblk_max, hipStream_t st) {
   const uint32_t P = p.P;
   p.queue = nullptr;
   p.n = P;
-  launch_init<R>(p, nblk_max, st);
+  launch_init<R>(p, k, nblk_max, st);
   c->last.launches++;
   uint32_t* qbuf[2] = {(uint32_t*)c->queue0.ptr, (uint32_t*)c->queue1.ptr};
   int qsel = 0;
@@ -538,8 +531,8 @@ rt_status render(rt_context* c, const rt_camera_desc* cam, const rt_render_param
     // the default schedule is persistent (k_persist); an explicit segments_per_launch selects the
     // launch-per-K-segments wavefront with HBM path state and live-slot compaction
     const bool persist = prm->segments_per_launch <= 0;
-    const StepKind kind{kernel_family(hdr, cam->mode, persist, prm->traversal == RT_TRAV_ORDERED), lamb_light_scene(hdr),
-                        no_light_scene(hdr), lamb_iso_light_scene(hdr), cs.stack_need};
+    const PathKernel kind = path_kernel(hdr, sizeof(typename WWord<R>::T), cam->mode, persist,
+                                        prm->traversal == RT_TRAV_ORDERED, cs.stack_need);
     if (!family_built(kind.fam))
       return set_err(c, RT_ERR_UNSUPPORTED,
                      std::string("this build (RT_DEV_ONLY) has no ") + family_name(kind.fam) + " kernels");
@@ -1237,6 +1230,26 @@ rt_status rt_set_timing(rt_context* c, int32_t enable) {
 
 uint32_t rt_rng_u32(uint64_t seed, uint32_t pixel, uint32_t sample, uint32_t dim) {
   return draw_u32(key_path(key_pixel(seed, pixel), key_sample(seed, sample)), dim);
+}
+
+// The tag of the path kernel a render of `desc` with these arguments would launch (path_kernel, as render() asks it),
+// in rt_dev_last_kernel's format; "" for a descriptor that does not compile or an unknown precision or traversal.
+// Compiles the descriptor on the host as rt_scene_check does and touches no GPU. A development entry point beside
+// rt_dev_last_kernel: for tests and scripts, not in rt_hip.h.
+void rt_dev_plan_kernel(const rt_scene_desc* desc, int32_t cam_mode, int32_t precision, int32_t traversal,
+                        int32_t segments_per_launch, char* buf, size_t n) {
+  if (!buf || n == 0) return;
+  buf[0] = 0;
+  CompiledScene cs;
+  std::string err;
+  if (!desc || (precision != RT_PREC_F32 && precision != RT_PREC_F64) ||
+      (traversal != RT_TRAV_AUTO && traversal != RT_TRAV_ORDERED) || compile_scene(desc, &cs, &err) != RT_OK)
+    return;
+  const bool f64 = precision == RT_PREC_F64;
+  const size_t word_bytes = f64 ? sizeof(WWord<double>::T) : sizeof(WWord<float>::T);
+  const PathKernel k = path_kernel(f64 ? cs.hdr64 : cs.hdr, word_bytes, cam_mode, segments_per_launch <= 0,
+                                   traversal == RT_TRAV_ORDERED, cs.stack_need);
+  std::snprintf(buf, n, "%s", path_kernel_tag(k, word_bytes).c_str());
 }
 
 }  // extern "C"

@@ -186,6 +186,10 @@ def load():
         # a development entry point beside the C ABI (not in include/rt_hip.h): Context.last_kernel
         lib.rt_dev_last_kernel.restype = None
         lib.rt_dev_last_kernel.argtypes = [ctypes.c_char_p, ctypes.c_size_t]
+        # ... and the kernel a render would launch, from the descriptor alone (no GPU): rt_amd.plan_kernel
+        lib.rt_dev_plan_kernel.restype = None
+        lib.rt_dev_plan_kernel.argtypes = [ctypes.POINTER(rt_scene_desc), c_int32, c_int32, c_int32, c_int32,
+                                           ctypes.c_char_p, ctypes.c_size_t]
         if lib.rt_abi_version() != ABI_VERSION:
             raise RuntimeError(f"{path} has ABI {lib.rt_abi_version()}, this binding expects {ABI_VERSION}: rebuild")
         _lib = lib

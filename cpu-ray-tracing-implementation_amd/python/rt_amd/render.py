@@ -272,3 +272,13 @@ def multi_plan(w, h, ndev, rank, tile_size=0):
     arr = (abi.rt_tile * max(1, n))()
     L.rt_multi_plan(w, h, ndev, tile_size, rank, arr, n)
     return [(t.x0, t.y0, t.width, t.height) for t in arr[:n]]
+
+
+def plan_kernel(desc, cam, precision=abi.RT_PREC_F32, traversal=0, segments_per_launch=0):
+    """The tag of the path kernel Context.render of scene `desc` through camera `cam` with these arguments would launch
+    (rt_dev_plan_kernel), in Context.last_kernel's format. The descriptor is compiled on the host: no GPU, no Context."""
+    buf = ctypes.create_string_buffer(128)
+    abi.load().rt_dev_plan_kernel(ctypes.byref(desc), cam.mode, precision, traversal, segments_per_launch, buf, len(buf))
+    if not buf.value:
+        raise ValueError("the descriptor does not compile, or an unknown precision or traversal")
+    return buf.value.decode()

@@ -173,7 +173,7 @@ def test_mesh_tree_in_hbm_lit_fp64_and_fp32(ctx):
     # C4's kernel (main.cc:439-498: triangles under a quad light, the wide tree in HBM) on a lit scene:
     # the C4 stand-in frame is dim (its light sits above the grids that close the atrium), so its own
     # parity rows compare mostly black pixels. 8,192 triangles are 24,576 primitive words, past the
-    # 4,096 an LDS-resident tree may hold (rt_kernels.hip launch_wide_k), so this takes the HBM tree --
+    # 4,096 an LDS-resident tree may hold (rt_plan.h wide_tree_in_lds), so this takes the HBM tree --
     # the C4 stand-in's kernel (triangles + quad) -- and every pixel sees lit triangles.
     from rt_amd.scene import SceneBuilder, perspective
     tris = terrain_triangles()

@@ -3,7 +3,8 @@ quad light and every path-kernel form that samples one (rt_device.h light_pdf / 
 scene_compile.cpp light_from). The scenes are light_scenes.py's; test_light_scenes.py pins them on the CPU.
 
 TABLE lists (scene, precision, traversal, schedule) -> the tag Context.last_kernel() must report, written out as
-launch_step / launch_wide / launch_k select at the time of writing: a silent change of selection fails here, and a
+rt_plan.h path_kernel selects at the time of writing (test_plan_tables.py holds that function to every row without a
+GPU; here the tag is the launched kernel's own): a silent change of selection fails here, and a
 test that believes it runs a form knows that it does. test_table_covers_every_light_and_form holds the table itself
 to its coverage: every Light::aligned code 1..6, with extents of both signs, in each form of FORMS and both
 precisions, and the off-axis, sphere and base-class lights in the families named there.

@@ -4,11 +4,12 @@ are material_scenes.py's; test_material_scenes.py pins them on the CPU and count
 the branches each one reaches.
 
 TABLE lists (scene, precision, traversal, segments_per_launch, camera or None) -> the tag Context.last_kernel() must
-report, written out from launch_step / launch_wide / launch_wide_k / launch_k: a silent change of selection fails
-here, and a row that believes it runs a form knows that it does. test_table_covers_every_branch_and_form holds the
+report, written out by hand from rt_plan.h path_kernel (test_plan_tables.py holds that function to every row without a
+GPU; here the tag is the launched kernel's own): a silent change of selection fails here, and a row that believes it
+runs a form knows that it does. test_table_covers_every_branch_and_form holds the
 table to its coverage: each event of REQUIRED, by the CPU test's counts, in a row of each shade form that compiles the
-branch in, in both precisions; and, with test_gpu_lights.py's table, every tag the launch functions can select
-(all_tags): LEFT_OUT, the tags no row launches with their reasons, is empty.
+branch in, in both precisions; and, with test_gpu_lights.py's table, every tag launch_step can launch
+(kernel_tags.all_tags): LEFT_OUT, the tags no row launches with their reasons, is empty.
 
 Each row is one small frame (16 spp, depth 8), held to test_gpu_lights.check_against_oracle's rules:
  - fp64: |d| <= 1e-9 max(1, |ref|); a flat, list or linear scene may miss it in at most 2 pixels, a BVH scene in under
@@ -24,6 +25,9 @@ import numpy as np
 import pytest
 
 import material_scenes as S
+from kernel_tags import (FLAT_GLOBAL, FLAT_LDS, FLAT_LL, LIN_ALL, LIN_LLI, LIN_QUAD, LIN_SPH, LIN_VOL, W_ALL, W_ALL_HBM,
+                         W_SPH, W_SPH_HBM, W_SPH_NL, W_SPH_NL_HBM, W_TQ, W_TQ_HBM, W_TQ_LL, W_TQ_LL_HBM, W_TRI,
+                         W_TRI_HBM, all_tags)
 import oracle
 import rt_amd
 import test_gpu_lights as lights
@@ -41,16 +45,7 @@ P = {F32: "f32", F64: "f64"}
 BOTH = (F32, F64)
 
 # ------------------------------------------------------------------ the traversals by name
-FLAT_LL, FLAT_LDS, FLAT_GLOBAL = "FlatTrav<{p},1,1>", "FlatTrav<{p},1,0>", "FlatTrav<{p},0,0>"
-LIN_QUAD, LIN_LLI, LIN_VOL = "LinearTrav<{p},0,0,0,0>", "LinearTrav<{p},0,0,1,1>", "LinearTrav<{p},0,0,1,0>"
-LIN_SPH, LIN_ALL = "LinearTrav<{p},1,0,0,0>", "LinearTrav<{p},1,1,1,0>"
-# WideTrav<R, SPH, TRI, QUAD, MOV, tree in LDS, LL, NL>
-W_SPH_NL, W_SPH_NL_HBM = "WideTrav<{p},1,0,0,0,1,0,1>", "WideTrav<{p},1,0,0,0,0,0,1>"
-W_SPH, W_SPH_HBM = "WideTrav<{p},1,0,0,0,1,0,0>", "WideTrav<{p},1,0,0,0,0,0,0>"
-W_TRI, W_TRI_HBM = "WideTrav<{p},0,1,0,0,1,0,0>", "WideTrav<{p},0,1,0,0,0,0,0>"
-W_TQ, W_TQ_HBM = "WideTrav<{p},0,1,1,0,1,0,0>", "WideTrav<{p},0,1,1,0,0,0,0>"
-W_TQ_LL, W_TQ_LL_HBM = "WideTrav<{p},0,1,1,0,1,1,0>", "WideTrav<{p},0,1,1,0,0,1,0>"
-W_ALL, W_ALL_HBM = "WideTrav<{p},1,1,1,1,1,0,0>", "WideTrav<{p},1,1,1,1,0,0,0>"
+# (FLAT_*, LIN_*, W_*: kernel_tags.py)
 # the binary BVH of a scene, by precision: fp32 keeps at most 256 nodes in LDS when the stack needs at most 16 entries;
 # otherwise the stack the tree needs (8, 16 or 32 entries)
 B_SMALL = {F32: "StackTrav<f32,16,1>", F64: "StackTrav<f64,8,0>"}    # spheres_small, mixed: 34 to 43 nodes, 8 entries
@@ -243,25 +238,6 @@ def row_id(r):
 
 
 # ------------------------------------------------------------------ the coverage the table is held to
-def all_tags():
-    """Every tag launch_step can select (rt_kernels.hip launch_step, launch_wide, launch_wide_k, launch_k), 96 in all."""
-    tags = set()
-    for p in ("f32", "f64"):
-        # the flat program has no extended form; its LDS forms exist in the persistent schedule only
-        tags |= {f"FlatTrav<{p},1,1> persist", f"FlatTrav<{p},1,0> persist", f"FlatTrav<{p},0,0> persist",
-                 f"FlatTrav<{p},0,0> step"}
-        for trav in (LIN_QUAD, LIN_VOL, LIN_SPH, LIN_ALL):
-            tags |= {trav.format(p=p) + camx + sched for camx in ("", " camx") for sched in (" persist", " step")}
-        tags |= {LIN_LLI.format(p=p) + camx + " persist" for camx in ("", " camx")}  # LLI: persist_body's shade only
-        # the wide tree: the persistent schedule and the perspective camera only (rt_plan.h kernel_family)
-        tags |= {w.format(p=p) + " persist" for w in (W_SPH_NL, W_SPH_NL_HBM, W_SPH, W_SPH_HBM, W_TRI, W_TRI_HBM, W_TQ,
-                                                       W_TQ_HBM, W_TQ_LL, W_TQ_LL_HBM, W_ALL, W_ALL_HBM)}
-        stacks = ["8,0", "16,0", "32,0"] + (["16,1"] if p == "f32" else [])
-        tags |= {f"StackTrav<{p},{s}>" + camx + sched for s in stacks for camx in ("", " camx")
-                 for sched in (" persist", " step")}
-    return tags
-
-
 # tags no row of either table launches, each with its reason
 LEFT_OUT = {}  # none: every tag is launched
 

@@ -420,7 +420,7 @@ def test_scenes_sit_on_their_side_of_each_limit():
     assert (I["backlight"]["flat_quads"], I["backlight"]["flat_boxes"]) == (6, 1)
     for name in ("glass_rot", "glass067_rot", "gloss_rot", "chain", "smoke_thick", "smoke_ball", "spheres_list"):
         assert family(name) == "linear", name
-    # FlatTrav<.,1,0>: 32 materials, 64 quads (rt_kernels.hip kLdsMats, kLdsQuads)
+    # FlatTrav<.,1,0>: 32 materials, 64 quads (rt_plan.h kFlatLds)
     for name, n in (("mats32", 32), ("mats33", 33)):
         desc, _ = S.SCENES[name]()
         mats = [desc.materials[i] for i in range(desc.num_materials)]
