@@ -1559,33 +1559,7 @@ template <class R, class Trav, class Job>
 __device__ __forceinline__ void query_loop(const DevScene<R>& sc, Job& job) {
   __shared__ Lds<Trav::kStack * kBlock> stk;
   QueryRay<R> s;
-  if constexpr (Job::kAny && Trav::kWide) {
-    using StackT = typename Trav::StackT;
-    extern __shared__ uint4 dyn_lds[];
-    StackT* wstk = Trav::fill(sc, dyn_lds) + threadIdx.x;  // (every lane of the block: it holds the barriers)
-    if (!job.valid()) return;
-    job.load(s);
-    const uint32_t root = Trav::root(sc);
-    WideRayT<R> ry{root, 0, job.bound(), kNoHit, 1u};
-#pragma unroll 1
-    for (;;) {
-      if (!Trav::template steps<true>(sc, (const Node<R>*)dyn_lds, s, wstk, ry)) continue;
-      job.template hit<false>(s, ry.tmax, ry.e, -1, 0u);
-      if (!job.advance()) break;
-      job.load(s);
-      ry = WideRayT<R>{root, 0, job.bound(), kNoHit, 1u};
-    }
-  } else if constexpr (Job::kAny) {
-#pragma unroll 1
-    for (bool more = job.valid(); more; more = job.advance()) {
-      job.load(s);
-      R t = job.bound();
-      uint32_t e, nm = 0;
-      int32_t inst;
-      Trav::template run<true>(sc, sc.nodes, s, Keys{s.ks}, stk.v + threadIdx.x, t, e, inst, nm);
-      job.template hit<Trav::kFlat>(s, t, e, inst, nm);
-    }
-  } else if constexpr (Trav::kWide) {
+  if constexpr (Trav::kWide) {
     // the resumable traversal, driven as persist_body drives it: a ray paused with the wave's laggards carries on
     // beside the rays the finished lanes take next
     using StackT = typename Trav::StackT;
@@ -1594,23 +1568,27 @@ __device__ __forceinline__ void query_loop(const DevScene<R>& sc, Job& job) {
     if (!job.valid()) return;
     job.load(s);
     const uint32_t root = Trav::root(sc);
-    WideRayT<R> ry{root, 0, Num<R>::inf(), kNoHit, 1u};
+    R hi = Num<R>::inf();  // the interval's upper end: open unless the job bounds it
+    if constexpr (Job::kAny) hi = job.bound();
+    WideRayT<R> ry{root, 0, hi, kNoHit, 1u};
 #pragma unroll 1
     for (;;) {
-      if (!Trav::steps(sc, (const Node<R>*)dyn_lds, s, wstk, ry)) continue;
+      if (!Trav::template steps<Job::kAny>(sc, (const Node<R>*)dyn_lds, s, wstk, ry)) continue;
       job.template hit<false>(s, ry.tmax, ry.e, -1, 0u);
       if (!job.advance()) break;
       job.load(s);
-      ry = WideRayT<R>{root, 0, Num<R>::inf(), kNoHit, 1u};
+      if constexpr (Job::kAny) hi = job.bound();
+      ry = WideRayT<R>{root, 0, hi, kNoHit, 1u};
     }
   } else {
 #pragma unroll 1
     for (bool more = job.valid(); more; more = job.advance()) {
       job.load(s);
-      R t;
+      R t;  // closest hit: an output alone
+      if constexpr (Job::kAny) t = job.bound();
       uint32_t e, nm = 0;
       int32_t inst;
-      Trav::run(sc, sc.nodes, s, Keys{s.ks}, stk.v + threadIdx.x, t, e, inst, nm);
+      Trav::template run<Job::kAny>(sc, sc.nodes, s, Keys{s.ks}, stk.v + threadIdx.x, t, e, inst, nm);
       job.template hit<Trav::kFlat>(s, t, e, inst, nm);
     }
   }
