@@ -9,6 +9,8 @@
 // rebuilding the live-slot queue. k_resolve: the per-pixel mean over the chunks, in chunk order. Each sample's
 // random numbers are keyed by (seed, global pixel, sample), so the image is bit-identical for any pool size,
 // tiling or GPU count. k_trace: closest hits of caller-given rays through the same traversals (rt_trace_rays).
+// k_persist over RaysOf<policy>: the persistent kernels with a batch of caller-given rays as their ray source, radiance
+// along those rays (rt_radiance).
 // k_camera_rays: the rays a render draws (rt_camera_rays); k_aov: per pixel the first-hit albedo, normal, depth and
 // ids over those rays, through k_trace's loop (rt_render_aov).
 #include <hip/hip_runtime.h>
@@ -314,9 +316,14 @@ __device__ __forceinline__ void item_range(const Params<R>& p, uint32_t item, ui
   end = min(first + (bulk ? p.chunk : p.tail_chunk), p.spp);
 }
 // the pixel's RNG key and the end of the item's samples: kept, or (LEAN) recomputed
-template <class R, class PS>
+// RAYS (here, begin_item, begin_sample): the kernel's paths start on the rays of a batch (rt_radiance), not on a
+// camera's. The path state's pixel word (xy) is then the ray's index in the batch, and its key pixel is that index
+// above p.ray_base.
+template <bool RAYS = false, class R, class PS>
 __device__ __forceinline__ uint32_t ka_of(const Params<R>& p, const PS& s) {
-  if constexpr (PS::kLean) {
+  if constexpr (PS::kLean && RAYS) {
+    return key_pixel(p.seed, p.ray_base + s.xy());
+  } else if constexpr (PS::kLean) {
     const uint32_t xy = s.xy();
     return key_pixel(p.seed, (xy >> 16) * p.W + (xy & 0xFFFFu));
   } else {
@@ -339,22 +346,24 @@ __device__ __forceinline__ uint32_t send_of(const Params<R>& p, const PS& s) {
 // development build (scripts/dev_item_clocks.py): each item's duration in wall-clock ticks (100 MHz), by item
 __device__ uint32_t* g_item_clk;
 #endif
-template <class R, class PS>
+template <bool RAYS = false, class R, class PS>
 __device__ __forceinline__ void begin_item(const Params<R>& p, PS& s, uint32_t item) {
 #ifdef RT_ITEM_CLOCKS
   s.t0_ = wall_clock64();
 #endif
   uint32_t lchunk, first, end;
   item_range(p, item, lchunk, first, end);
-  const uint32_t xy = p.pixmap[item - lchunk * p.npix];
+  // a batch's "pixel" is the ray's index itself: no pixel map, and no per-item camera base below
+  uint32_t xy = item - lchunk * p.npix;
+  if constexpr (!RAYS) xy = p.pixmap[xy];
   s.set_item(item);
   s.set_sample(first);
   s.set_xy(xy);
   if constexpr (!PS::kLean) {
     s.set_send(end);
-    s.set_ka(key_pixel(p.seed, (xy >> 16) * p.W + (xy & 0xFFFFu)));
+    s.set_ka(key_pixel(p.seed, RAYS ? p.ray_base + xy : (xy >> 16) * p.W + (xy & 0xFFFFu)));
   }
-  pixel_base(p, s, xy);
+  if constexpr (!RAYS) pixel_base(p, s, xy);
 }
 
 // camera::generate_ray for the orthonormal, fisheye and lens models (camera.h:252-290), reading
@@ -401,16 +410,29 @@ RT_EXT_FN void camera_ray(const CamDev* cp, uint32_t ks, uint32_t x, uint32_t y,
   }
 }
 
+// The first ray of a sample of a ray batch (RAYS): ray s.xy() of p.rays, 64 bytes as load_query reads them, o, d and the
+// time in fp64, rounded to R below as a camera ray is. The path's key is a camera sample's, (seed, pixel, sample), and
+// its draws keep their dimensions: 0 and 1, the pixel jitter, are never drawn; 2, the ray time, is drawn as
+// camera::generate_ray draws it only where the stored time is NaN. tmax is not read: the first segment runs over
+// interval(0.001, inf) like every other (camera.h:198).
+template <class R, class PS>
+__device__ __forceinline__ void batch_ray(const Params<R>& p, const PS& s, V<double>& o, V<double>& d, double& tm) {
+  const double2* q = (const double2*)(p.rays + 8ull * s.xy());  // 16-byte aligned (rt_radiance checks)
+  const double2 r0 = q[0], r1 = q[1], r2 = q[2];
+  o = mkv(r0.x, r0.y, r1.x);
+  d = mkv(r1.y, r2.x, r2.y);
+  tm = q[3].x;
+  if (tm != tm) tm = to_unit<double>(draw_u32(s.ks, 2));
+}
+
 // camera::generate_ray, perspective mode (camera.h:244-251,293): sample s.sample of the slot's pixel
 template <class R, bool CAMX, class PS>
-__device__ __forceinline__ void begin_sample(const Params<R>& p, PS& s) {
-  s.ks = key_path(ka_of(p, s), key_sample(p.seed, p.first_sample + s.sample()));
+__device__ __forceinline__ void pixel_ray(const Params<R>& p, const PS& s, V<double>& o, V<double>& d, double& tm) {
   // In fp64 for both paths: fp32 gets the correctly rounded ray, a few ulp less error on every
   // camera ray, which otherwise shows up as paths crossing a checker line or edge differently.
   const double ox = to_unit<double>(draw_u32(s.ks, 0)) - 0.5;  // sample_square (camera.h:293)
   const double oy = to_unit<double>(draw_u32(s.ks, 1)) - 0.5;
-  V<double> o = ld_here(&p.camx->pos), d;
-  double tm;
+  o = ld_here(&p.camx->pos);
   if (!CAMX || p.cam_mode == RT_CAM_PERSPECTIVE) {  // camera.h:245-251
     const V<double> du = ld_here(&p.camx->du), dv = ld_here(&p.camx->dv);
     if constexpr (!PS::kLean) {
@@ -424,6 +446,18 @@ __device__ __forceinline__ void begin_sample(const Params<R>& p, PS& s) {
     const uint32_t xy = s.xy();
     camera_ray(p.camx, s.ks, xy & 0xFFFFu, xy >> 16, ox, oy, o, d, tm);
   }
+}
+// A new sample for the slot: its key and its first ray, the camera's or (RAYS; CAMX is then the scene's textures
+// alone) the batch's
+template <class R, bool CAMX, bool RAYS = false, class PS>
+__device__ __forceinline__ void begin_sample(const Params<R>& p, PS& s) {
+  s.ks = key_path(ka_of<RAYS>(p, s), key_sample(p.seed, p.first_sample + s.sample()));
+  V<double> o, d;
+  double tm;
+  if constexpr (RAYS)
+    batch_ray(p, s, o, d, tm);
+  else
+    pixel_ray<R, CAMX>(p, s, o, d, tm);
   s.o = mkv(R(o.x), R(o.y), R(o.z));
   s.d = mkv(R(d.x), R(d.y), R(d.z));
   s.tm = R(tm);
@@ -479,10 +513,12 @@ struct ShadeOf {
   static constexpr bool kFlat = Trav::kFlat, kMoving = Trav::kMoving, kLL = Trav::kLL, kNL = Trav::kNL,
                         kLLI = Trav::kLLI;
   static constexpr bool kMatsLds = Trav::kTablesLds || Trav::kLL;
+  static constexpr bool kRays = Trav::kRays;  // the next sample starts on a ray of the batch (begin_sample RAYS)
 };
 template <bool FLAT>
 struct ShadeGeneral {
   static constexpr bool kFlat = FLAT, kMoving = true, kLL = false, kNL = false, kLLI = false, kMatsLds = false;
+  static constexpr bool kRays = false;
 };
 template <class R, bool CAMX, class Cfg, class PS>
 __device__ bool shade(const Params<R>& p, PS& s, R t, uint32_t e, int32_t inst, uint32_t nm = 0,
@@ -878,13 +914,13 @@ __device__ bool shade(const Params<R>& p, PS& s, R t, uint32_t e, int32_t inst, 
         return false;
       }
     } else {
-      begin_item(p, s, nx);
+      begin_item<Cfg::kRays>(p, s, nx);
     }
   }
   // (round 5: regenerating the finished lanes of a wave in batches -- a lane waiting idle until 16 or 32 of
   // its wave's lanes had finished -- was slower, C2 fp64 28.33 -> 28.46 / 29.95 ms/frame, r05e: the lanes a
   // wait idles in trace and shade cost more than the regeneration's 41 % lane use)
-  begin_sample<R, CAMX>(p, s);
+  begin_sample<R, CAMX, Cfg::kRays>(p, s);
   // kInPlace: a retiring lane generated a ray too (of its last item: registers only, never traced), so that it also
   // leaves with a state written here
   if constexpr (kInPlace) {
@@ -920,6 +956,13 @@ struct TravDefaults {
   // occlusion queries: the policy also has k_occluded's closest-hit form (EARLY = false), which launch_occluded takes
   // where occlusion_early_exit (rt_plan.h) refuses the any-hit form. A policy without it always takes the any-hit form.
   [[maybe_unused]] static constexpr bool kClosestOccl = false;
+  static constexpr bool kRays = false;  // RaysOf: the paths start on the rays of a batch, not on a camera's
+};
+// The policy `Trav` for a ray batch (rt_radiance): the same traversal, tables, path state and shade form, in a kernel of
+// its own whose begin_item / begin_sample read the batch (RAYS) -- so the camera kernels hold no trace of it.
+template <class Trav>
+struct RaysOf : Trav {
+  static constexpr bool kRays = true;
 };
 template <class R, bool SPH, bool TRI, bool VOL, bool LLI = false>
 struct LinearTrav : TravDefaults {
@@ -1314,8 +1357,8 @@ __device__ __forceinline__ void persist_body(const Params<R>& p) {
   if (item0 < p.n_items) {
     Path<R, Trav::kColdLds, Trav::kLean, Trav::kNoRad, Trav::kThrLds> s;
     s.set_acc(mkv(R(0), R(0), R(0)));
-    begin_item(p, s, item0);
-    begin_sample<R, CAMX>(p, s);
+    begin_item<Trav::kRays>(p, s, item0);
+    begin_sample<R, CAMX, Trav::kRays>(p, s);
     if constexpr (Trav::kWide) {
       // resumable traversal: a ray paused with the wave's laggards carries on after the others shade
       using StackT = typename Trav::StackT;
@@ -2017,10 +2060,14 @@ template <class R, bool SPH, bool TRI, bool QUAD, bool MOV, bool LDSN, bool LL, 
 struct TravName<WideTrav<R, SPH, TRI, QUAD, MOV, LDSN, LL, NL>> {
   static std::string get() { return trav_tag<R>("WideTrav", SPH, TRI, QUAD, MOV, LDSN, LL, NL); }
 };
+template <class Trav>
+struct TravName<RaysOf<Trav>> {  // "... rays persist": the policy's name, then the ray source (kernel_tag)
+  static std::string get() { return TravName<Trav>::get(); }
+};
 template <class Trav, bool CAMX>
 const char* kernel_tag(bool persist) {  // built once per kernel: a wavefront render launches its kernel many times
-  static const std::string tag[2] = {TravName<Trav>::get() + (CAMX ? " camx step" : " step"),
-                                     TravName<Trav>::get() + (CAMX ? " camx persist" : " persist")};
+  static const std::string form = std::string(CAMX ? " camx" : "") + (Trav::kRays ? " rays" : "");
+  static const std::string tag[2] = {TravName<Trav>::get() + form + " step", TravName<Trav>::get() + form + " persist"};
   return tag[persist ? 1 : 0].c_str();
 }
 // tag of the last path kernel launched on this host thread
@@ -2078,24 +2125,37 @@ uint32_t spill_grid(const DevScene<R>& sc, uint32_t grid) {
   return sc.wide_spill ? std::min<uint32_t>(grid, sc.spill_lanes / kBlock) : grid;
 }
 // The wide kernel of the plan's primitive kinds and shade class, over a tree in LDS or in HBM
-template <class R, bool SPH, bool TRI, bool QUAD, bool MOV, bool LL = false, bool NL = false>
-void launch_wide_k(const Params<R>& p, const PathKernel& k, uint32_t grid, hipStream_t st) {
+template <class R, class InLds, class InHbm>
+void launch_wide_t(const Params<R>& p, const PathKernel& k, uint32_t grid, hipStream_t st) {
   if (k.lds) {
-    using InLds = WideTrav<R, SPH, TRI, QUAD, MOV, true, LL, NL>;
     launch_one<InLds, false>(k_persist_occ<R, InLds, false>, p, grid, st, wide_lds_bytes(p.sc, true));
     return;
   }
-  using InHbm = WideTrav<R, SPH, TRI, QUAD, MOV, false, LL, NL>;
   launch_one<InHbm, false>(k_persist_occ<R, InHbm, false>, p, spill_grid(p.sc, grid), st, wide_lds_bytes(p.sc, false));
+}
+template <class R, bool SPH, bool TRI, bool QUAD, bool MOV, bool LL = false, bool NL = false>
+void launch_wide_k(const Params<R>& p, const PathKernel& k, uint32_t grid, hipStream_t st) {
+  using InLds = WideTrav<R, SPH, TRI, QUAD, MOV, true, LL, NL>;
+  using InHbm = WideTrav<R, SPH, TRI, QUAD, MOV, false, LL, NL>;
+  if (k.rays)
+    launch_wide_t<R, RaysOf<InLds>, RaysOf<InHbm>>(p, k, grid, st);
+  else
+    launch_wide_t<R, InLds, InHbm>(p, k, grid, st);
 }
 // A flat, linear or binary-BVH kernel in the plan's form (base or extended) and schedule
 template <class R, class Trav>
 void launch_k(const Params<R>& p, const PathKernel& k, uint32_t grid, hipStream_t st) {
+  if constexpr (!Trav::kRays) {
+    if (k.rays) {  // a ray batch: the same choices over the policy's RAYS form (persistent only: radiance_kernel)
+      launch_k<R, RaysOf<Trav>>(p, k, grid, st);
+      return;
+    }
+  }
   if (k.camx) {  // (the flat program has no CAMX form: path_kernel)
     if constexpr (!Trav::kFlat) {
       if (k.persist)
         launch_one<Trav, true>(k_persist_occ<R, Trav, true>, p, grid, st);
-      else
+      else if constexpr (!Trav::kRays)
         launch_one<Trav, true>(k_step_occ<R, Trav, true>, p, grid, st);
     }
     return;
@@ -2105,7 +2165,7 @@ void launch_k(const Params<R>& p, const PathKernel& k, uint32_t grid, hipStream_
       launch_one<Trav, false>(k_persist_occ<R, Trav, false>, p, grid, st);
     else
       launch_one<Trav, false>(k_persist<R, Trav, false>, p, grid, st);
-  } else {
+  } else if constexpr (!Trav::kRays) {
     if constexpr (Trav::kWaves > 1)
       launch_one<Trav, false>(k_step_occ<R, Trav, false>, p, grid, st);
     else

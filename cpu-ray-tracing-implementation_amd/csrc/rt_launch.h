@@ -68,6 +68,12 @@ struct LaunchParams {
   uint32_t* heads;  // kHeads dequeue counters, kHeadStride words apart (persistent schedule)
   uint64_t seg_cap;  // a lane never needs more segments than this (its items * chunk * max_depth)
   uint32_t* fault;   // set when a lane hits seg_cap (internal error, reported by the host)
+  // A ray batch (rt_radiance; PathKernel::rays): the lanes' first segments are caller-given rays instead of camera
+  // rays. rays: [npix][8] doubles o, d, time, tmax as TraceParams' (16-byte aligned); the batch is laid out as an
+  // image W wide whose pixel y * W + x is ray y * W + x, keyed as pixel ray_base + y * W + x. Last in the struct: the
+  // camera kernels read neither, and every field they read keeps its place in the kernarg segment.
+  const double* rays;
+  uint32_t ray_base;
 };
 constexpr int32_t kPersist = 2;
 

@@ -168,6 +168,7 @@ struct PathKernel {
   uint32_t kinds;  // wide tree: the WK_* primitive kinds the kernel tests, one of six sets; else 0
   bool camx;       // the extended form (the linear program and the binary BVH alone)
   bool persist;    // the persistent schedule, else the wavefront schedule
+  bool rays;       // the first segments are caller-given rays (rt_radiance; radiance_kernel), not camera rays
 };
 // The path kernel a render launches. h: the header of the blob the precision reads (hdr or hdr64: an fp64 flat scene
 // stores a room's walls as one room record, so the two can fall on different sides of the flat tables' limits);
@@ -213,14 +214,23 @@ inline PathKernel path_kernel(const SceneHeader& h, size_t word_bytes, int32_t c
   }
   return k;
 }
+// The path kernel a ray batch launches (rt_radiance): the one a perspective render of the scene takes on the persistent
+// schedule -- the same family, shade form, LDS use and stack, the extended form by the scene's textures alone (a batch
+// has no camera model) -- in its form whose first segments are the caller's rays.
+inline PathKernel radiance_kernel(const SceneHeader& h, size_t word_bytes, bool ordered, int stack_need) {
+  PathKernel k = path_kernel(h, word_bytes, RT_CAM_PERSPECTIVE, true, ordered, stack_need);
+  k.rays = true;
+  return k;
+}
 // The kernel's tag as rt_dev_last_kernel reports it (rt_kernels.hip kernel_tag): the traversal policy with every
 // template argument in order (the precision first, bools as 0 / 1), "camx" for the extended form, and the schedule:
-// "WideTrav<f64,0,1,1,0,1,1,0> persist", "LinearTrav<f32,1,1,1,0> camx step".
+// "WideTrav<f64,0,1,1,0,1,1,0> persist", "LinearTrav<f32,1,1,1,0> camx step"; a ray batch's has "rays" before the
+// schedule, "FlatTrav<f64,1,1> rays persist".
 inline std::string path_kernel_tag(const PathKernel& k, size_t word_bytes) {
   auto trav = [&](const char* name, std::initializer_list<int> args) {
     std::string s = std::string(name) + (word_bytes == 32 ? "<f64" : "<f32");
     for (int a : args) s += "," + std::to_string(a);
-    return s + ">" + (k.camx ? " camx" : "") + (k.persist ? " persist" : " step");
+    return s + ">" + (k.camx ? " camx" : "") + (k.rays ? " rays" : "") + (k.persist ? " persist" : " step");
   };
   const bool sph = k.fam == KF_LIN_SPH || k.fam == KF_LIN_ALL, all = k.fam == KF_LIN_ALL;
   switch (k.fam) {

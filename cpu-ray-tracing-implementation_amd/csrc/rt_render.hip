@@ -1,6 +1,6 @@
 // rt_render.hip -- the host side of librt_hip.so: contexts and their device buffers, render<R>() and its two
-// schedules, the query path (trace_rays<R>(), occluded<R>(), camera_rays(), render_aov<R>()), and the C ABI of
-// include/rt_hip.h with its argument checks. It contains no kernel: what a render launches goes through
+// schedules (over a camera's tiles, or over a ray batch: rt_radiance), the query path (trace_rays<R>(), occluded<R>(),
+// camera_rays(), render_aov<R>()), and the C ABI of include/rt_hip.h with its argument checks. It contains no kernel: what a render launches goes through
 // rt_launch.h (rt_kernels.hip), and its item layout and kernel family come from rt_plan.h.
 #include <hip/hip_runtime.h>
 
@@ -499,9 +499,20 @@ rt_status scene_to_device(rt_context* c, bool f64, hipStream_t st, LaneQuery* lq
   return RT_OK;
 }
 
+// A ray batch in place of a camera and tiles (rt_radiance): `n` rays (0 < n < 2^31) at `rays`, device memory when
+// on_device (else the call stages them in q_rays), ray i keyed as pixel ray_base + i. render() lays the batch out as the
+// n "pixels" of its call -- item planner, passes, partial sums and resolve as for an image -- and the kernel reads ray
+// i where a camera kernel would read pixel i of the pixel map.
+struct RayBatch {
+  const double* rays;
+  uint32_t n, ray_base;
+  bool on_device;
+};
+
+// cam and tiles, or (cam = tiles = nullptr) the ray batch rb
 template <class R>
 rt_status render(rt_context* c, const rt_camera_desc* cam, const rt_render_params* prm, const rt_tile* tiles,
-                 int32_t ntiles, void* out, int32_t out_dev, hipStream_t st) {
+                 int32_t ntiles, void* out, int32_t out_dev, hipStream_t st, const RayBatch* rb = nullptr) {
   const bool f64 = sizeof(R) == 8;
   const CompiledScene& cs = c->scene;
   const SceneHeader& hdr = f64 ? cs.hdr64 : cs.hdr;
@@ -512,8 +523,8 @@ rt_status render(rt_context* c, const rt_camera_desc* cam, const rt_render_param
   if ((s = scene_to_device(c, f64, st, &lq)) != RT_OK) return s;
 
   // pixel map: tiles packed in order, row-major inside each tile (expanded by k_pixmap)
-  uint64_t npix64 = 0;
-  const std::vector<uint4> tl = pack_tiles(tiles, ntiles, npix64);
+  uint64_t npix64 = rb ? rb->n : 0;
+  const std::vector<uint4> tl = rb ? std::vector<uint4>() : pack_tiles(tiles, ntiles, npix64);
   if (npix64 >= (1ull << 31)) return set_err(c, RT_ERR_INVALID_ARGUMENT, "too many pixels in one call");
   const uint32_t npix = (uint32_t)npix64;
   if (npix == 0) return RT_OK;
@@ -531,14 +542,17 @@ rt_status render(rt_context* c, const rt_camera_desc* cam, const rt_render_param
     // the default schedule is persistent (k_persist); an explicit segments_per_launch selects the
     // launch-per-K-segments wavefront with HBM path state and live-slot compaction
     const bool persist = prm->segments_per_launch <= 0;
-    const PathKernel kind = path_kernel(hdr, sizeof(typename WWord<R>::T), cam->mode, persist,
-                                        prm->traversal == RT_TRAV_ORDERED, cs.stack_need);
+    const bool ordered = prm->traversal == RT_TRAV_ORDERED;
+    const PathKernel kind = rb ? radiance_kernel(hdr, sizeof(typename WWord<R>::T), ordered, cs.stack_need)
+                               : path_kernel(hdr, sizeof(typename WWord<R>::T), cam->mode, persist, ordered, cs.stack_need);
     if (!family_built(kind.fam))
       return set_err(c, RT_ERR_UNSUPPORTED,
                      std::string("this build (RT_DEV_ONLY) has no ") + family_name(kind.fam) + " kernels");
     // the item layout and the passes (the full image's pixels decide the item size, not this call's tiles)
+    // (a batch is its own full image: with samples_per_item given, the layout depends on spp alone)
     const ItemPlan plan = plan_items(spp, prm->samples_per_item, kind.fam == KF_FLAT,
-                                     (uint64_t)cam->image_width * (uint64_t)cam->image_height, npix, sizeof(R), env_knobs());
+                                     rb ? (uint64_t)npix : (uint64_t)cam->image_width * (uint64_t)cam->image_height, npix,
+                                     sizeof(R), env_knobs());
     const uint32_t n_items = npix * plan.cpp;  // items of the largest pass
     uint32_t P = prm->pool_slots > 0 ? (uint32_t)prm->pool_slots
                  : persist       ? kAutoPersistLanes
@@ -558,7 +572,7 @@ rt_status render(rt_context* c, const rt_camera_desc* cam, const rt_render_param
     c->last.passes += plan.passes;
     c->last.partial_bytes = plan.partial_bytes;
     if ((s = ensure(c, c->blk, 4ull * (nblk_max + 2))) != RT_OK) return s;
-    if ((s = pixel_map(c, tl, npix, st)) != RT_OK) return s;
+    if (!rb && (s = pixel_map(c, tl, npix, st)) != RT_OK) return s;
 
     unsigned char* sp = (unsigned char*)c->state.ptr;
     LaunchParams<R> p{};
@@ -586,13 +600,24 @@ rt_status render(rt_context* c, const rt_camera_desc* cam, const rt_render_param
     p.tail_chunk = plan.tail_chunk;
     p.spp = spp;
     p.first_sample = (uint32_t)std::max(0, prm->first_sample);
-    p.W = (uint32_t)cam->image_width;
     p.max_depth = prm->max_depth;
     p.seed = prm->seed;
-    if ((s = camera_view(c, cam, st)) != RT_OK) return s;
-    p.cam_mode = c->cam_host.mode;
-    p.camx = (const CamDev*)c->camx.ptr;
-    if (p.cam_mode == RT_CAM_PERSPECTIVE) p.sc.cam64 = p.camx;
+    if (rb) {  // no camera: cam64 stays null, so a near-edge quad re-decision (quad_edge64) takes the given ray, as a query's
+      p.rays = rb->rays;
+      p.ray_base = rb->ray_base;
+      p.cam_mode = RT_CAM_PERSPECTIVE;
+      if (!rb->on_device) {
+        if ((s = ensure(c, c->q_rays, 64ull * npix)) != RT_OK) return s;
+        p.rays = (const double*)c->q_rays.ptr;
+        RT_HIP(c, hipMemcpyAsync(c->q_rays.ptr, rb->rays, 64ull * npix, hipMemcpyHostToDevice, st));
+      }
+    } else {
+      p.W = (uint32_t)cam->image_width;
+      if ((s = camera_view(c, cam, st)) != RT_OK) return s;
+      p.cam_mode = c->cam_host.mode;
+      p.camx = (const CamDev*)c->camx.ptr;
+      if (p.cam_mode == RT_CAM_PERSPECTIVE) p.sc.cam64 = p.camx;
+    }
     p.seg_shards = (unsigned long long*)c->counters.ptr;
     p.K = prm->segments_per_launch > 0 ? std::min(prm->segments_per_launch, 64) : kAutoSegments;
     if (c->timing && c->ev_used > 4096 && (s = settle(c)) != RT_OK) return s;  // bound the pending events
@@ -604,7 +629,9 @@ rt_status render(rt_context* c, const rt_camera_desc* cam, const rt_render_param
       p.heads = (uint32_t*)c->heads.ptr;
     }
     // the launch lanes (rt_plan.h lane_plan): asked per launch, so the passes of a call alternate too
-    lq.knob = env_frame_overlap();
+    // A ray batch stays on the caller's stream: its rays are the caller's, written on that stream, and a lane would
+    // have to wait for them before every launch -- there is no unchanged-input case for the lanes to overlap.
+    lq.knob = env_frame_overlap() && !rb;
     lq.device_out = out_dev != 0;
     lq.persist = persist;
     lq.shared_scratch = p.sc.wide_spill != nullptr;
@@ -1149,6 +1176,39 @@ rt_status rt_occluded(rt_context* c, const rt_trace_params* prm, const double* r
   });
 }
 
+rt_status rt_radiance(rt_context* c, const rt_radiance_params* prm, const double* rays, int64_t nrays, void* out_rgb,
+                      void* stream) {
+  if (!c) return set_err(nullptr, RT_ERR_INVALID_ARGUMENT, "null context");
+  if (!prm || !rays || !out_rgb) return set_err(c, RT_ERR_INVALID_ARGUMENT, "null argument");
+  rt_status s;
+  if (nrays < 0 || (uint64_t)prm->ray_base + (uint64_t)nrays > (1ull << 32))
+    return set_err(c, RT_ERR_INVALID_ARGUMENT, "nrays negative, or ray_base + nrays above 2^32");
+  if ((s = check_spp(c, prm->spp)) != RT_OK) return s;
+  if (prm->max_depth < 0) return set_err(c, RT_ERR_INVALID_ARGUMENT, "max_depth must not be negative");
+  // the item planner's limit: a call's pixels -- here its rays -- below 2^31 (any spp: the chunks then come in passes)
+  if ((s = check_nrays(c, nrays)) != RT_OK) return s;
+  if ((s = check_precision_traversal(c, prm->precision, prm->traversal)) != RT_OK) return s;
+  if (prm->on_device && ((uintptr_t)rays | (uintptr_t)out_rgb) % 16 != 0)  // the kernel reads a ray as 16-byte words
+    return set_err(c, RT_ERR_INVALID_ARGUMENT, "device rays and out_rgb must be 16-byte aligned");
+  if ((s = check_scene(c)) != RT_OK) return s;
+  if (nrays == 0) return RT_OK;
+  RT_HIP(c, hipSetDevice(c->device));
+  hipStream_t st = call_stream(c, stream, prm->on_device != 0);
+  // a render's parameters: the persistent schedule (no segments_per_launch), the automatic grid
+  rt_render_params rp{};
+  rp.spp = prm->spp;
+  rp.max_depth = prm->max_depth;
+  rp.seed = prm->seed;
+  rp.precision = prm->precision;
+  rp.first_sample = prm->first_sample;
+  rp.samples_per_item = prm->samples_per_item;
+  rp.traversal = prm->traversal;
+  const RayBatch rb{rays, (uint32_t)nrays, prm->ray_base, prm->on_device != 0};
+  return by_precision(c, prm->precision, true, [&](auto r) {
+    return render<decltype(r)>(c, nullptr, &rp, nullptr, 0, out_rgb, prm->on_device, st, &rb);
+  });
+}
+
 rt_status rt_camera_rays(rt_context* c, const rt_camera_desc* cam, uint64_t seed, int32_t first_sample, int32_t spp,
                          const rt_tile* tiles, int32_t ntiles, double* out_rays, int32_t on_device, void* stream) {
   if (!c) return set_err(nullptr, RT_ERR_INVALID_ARGUMENT, "null context");
@@ -1249,6 +1309,21 @@ void rt_dev_plan_kernel(const rt_scene_desc* desc, int32_t cam_mode, int32_t pre
   const size_t word_bytes = f64 ? sizeof(WWord<double>::T) : sizeof(WWord<float>::T);
   const PathKernel k = path_kernel(f64 ? cs.hdr64 : cs.hdr, word_bytes, cam_mode, segments_per_launch <= 0,
                                    traversal == RT_TRAV_ORDERED, cs.stack_need);
+  std::snprintf(buf, n, "%s", path_kernel_tag(k, word_bytes).c_str());
+}
+// The same for rt_radiance on a scene of `desc` (radiance_kernel): the tag a perspective render's kernel has, with
+// "rays" before the schedule.
+void rt_dev_plan_radiance(const rt_scene_desc* desc, int32_t precision, int32_t traversal, char* buf, size_t n) {
+  if (!buf || n == 0) return;
+  buf[0] = 0;
+  CompiledScene cs;
+  std::string err;
+  if (!desc || (precision != RT_PREC_F32 && precision != RT_PREC_F64) ||
+      (traversal != RT_TRAV_AUTO && traversal != RT_TRAV_ORDERED) || compile_scene(desc, &cs, &err) != RT_OK)
+    return;
+  const bool f64 = precision == RT_PREC_F64;
+  const size_t word_bytes = f64 ? sizeof(WWord<double>::T) : sizeof(WWord<float>::T);
+  const PathKernel k = radiance_kernel(f64 ? cs.hdr64 : cs.hdr, word_bytes, traversal == RT_TRAV_ORDERED, cs.stack_need);
   std::snprintf(buf, n, "%s", path_kernel_tag(k, word_bytes).c_str());
 }
 

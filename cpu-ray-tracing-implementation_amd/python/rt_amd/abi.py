@@ -95,6 +95,12 @@ class rt_aov_params(ctypes.Structure):
                 ("traversal", c_int32), ("on_device", c_int32), ("pad_", c_int32)]
 
 
+class rt_radiance_params(ctypes.Structure):
+    _fields_ = [("seed", c_uint64), ("spp", c_int32), ("first_sample", c_int32), ("max_depth", c_int32),
+                ("precision", c_int32), ("traversal", c_int32), ("samples_per_item", c_int32), ("ray_base", c_uint32),
+                ("on_device", c_int32)]
+
+
 # rt_trace_family_kind
 RT_TRACE_FLAT, RT_TRACE_LINEAR, RT_TRACE_WIDE_LDS, RT_TRACE_WIDE_HBM, RT_TRACE_STACK = range(5)
 TRACE_FAMILY_NAMES = ("FLAT", "LINEAR", "WIDE_LDS", "WIDE_HBM", "STACK")
@@ -120,6 +126,8 @@ SIGNATURES = {
                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "rt_trace_family": (c_int32, [ctypes.c_void_p, c_int32, c_int32]),
     "rt_occluded": (c_int32, [ctypes.c_void_p, ctypes.POINTER(rt_trace_params), ctypes.c_void_p, ctypes.c_int64,
+                              ctypes.c_void_p, ctypes.c_void_p]),
+    "rt_radiance": (c_int32, [ctypes.c_void_p, ctypes.POINTER(rt_radiance_params), ctypes.c_void_p, ctypes.c_int64,
                               ctypes.c_void_p, ctypes.c_void_p]),
     "rt_camera_rays": (c_int32, [ctypes.c_void_p, ctypes.POINTER(rt_camera_desc), c_uint64, c_int32, c_int32,
                                  ctypes.POINTER(rt_tile), c_int32, ctypes.c_void_p, c_int32, ctypes.c_void_p]),
@@ -190,6 +198,10 @@ def load():
         lib.rt_dev_plan_kernel.restype = None
         lib.rt_dev_plan_kernel.argtypes = [ctypes.POINTER(rt_scene_desc), c_int32, c_int32, c_int32, c_int32,
                                            ctypes.c_char_p, ctypes.c_size_t]
+        # ... and the kernel a ray batch would launch: rt_amd.plan_radiance_kernel
+        lib.rt_dev_plan_radiance.restype = None
+        lib.rt_dev_plan_radiance.argtypes = [ctypes.POINTER(rt_scene_desc), c_int32, c_int32, ctypes.c_char_p,
+                                             ctypes.c_size_t]
         if lib.rt_abi_version() != ABI_VERSION:
             raise RuntimeError(f"{path} has ABI {lib.rt_abi_version()}, this binding expects {ABI_VERSION}: rebuild")
         _lib = lib

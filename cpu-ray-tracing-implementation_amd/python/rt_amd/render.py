@@ -127,8 +127,25 @@ class Context:
         self._check(self.lib.rt_occluded(self.h, ctypes.byref(prm), sp, n, op, stream))
         return out
 
+    def radiance(self, rays, spp, max_depth, seed=1, precision=abi.RT_PREC_F32, traversal=0, first_sample=0,
+                 samples_per_item=0, ray_base=0, stream=None):
+        """Path-traced radiance along `rays` (rt_radiance), rows as trace_rays takes them (tmax is not read; a NaN time
+        makes every sample draw its own) -> (n, 3) of the precision's dtype: per ray the mean of ray_color over samples
+        [first_sample, first_sample + spp), ray i keyed as pixel ray_base + i of a render with this seed.
+
+        A C-contiguous numpy array takes the host path and returns a numpy array; a float64 torch tensor on the
+        context's device takes the device path, ordered on `stream` (default torch's current stream), and returns a
+        tensor on that device."""
+        dev, n, src, sp, stream = self._ray_source(rays, stream)
+        prm = abi.rt_radiance_params(seed=seed, spp=spp, first_sample=first_sample, max_depth=max_depth,
+                                     precision=precision, traversal=traversal, samples_per_item=samples_per_item,
+                                     ray_base=ray_base, on_device=int(dev is not None))
+        out, op = self._output(n, (3,), "float64" if precision == abi.RT_PREC_F64 else "float32", dev)
+        self._check(self.lib.rt_radiance(self.h, ctypes.byref(prm), sp, n, op, stream))
+        return out
+
     def _ray_source(self, rays, stream):
-        """What trace_rays and occluded make of their `rays` and `stream`: (the rays' torch device, or None for the
+        """What trace_rays, occluded and radiance make of their `rays` and `stream`: (the rays' torch device, or None for the
         host path; n; the array to read -- one padding row for n = 0: an empty array still hands over a valid pointer,
         since the call checks its arguments and launches nothing -- and its pointer; the stream handle or None)."""
         if isinstance(rays, np.ndarray):
@@ -279,6 +296,16 @@ def plan_kernel(desc, cam, precision=abi.RT_PREC_F32, traversal=0, segments_per_
     (rt_dev_plan_kernel), in Context.last_kernel's format. The descriptor is compiled on the host: no GPU, no Context."""
     buf = ctypes.create_string_buffer(128)
     abi.load().rt_dev_plan_kernel(ctypes.byref(desc), cam.mode, precision, traversal, segments_per_launch, buf, len(buf))
+    if not buf.value:
+        raise ValueError("the descriptor does not compile, or an unknown precision or traversal")
+    return buf.value.decode()
+
+
+def plan_radiance_kernel(desc, precision=abi.RT_PREC_F32, traversal=0):
+    """The tag of the path kernel Context.radiance on scene `desc` would launch (rt_dev_plan_radiance): plan_kernel's
+    for a perspective render on the persistent schedule, with "rays" before the schedule. No GPU, no Context."""
+    buf = ctypes.create_string_buffer(128)
+    abi.load().rt_dev_plan_radiance(ctypes.byref(desc), precision, traversal, buf, len(buf))
     if not buf.value:
         raise ValueError("the descriptor does not compile, or an unknown precision or traversal")
     return buf.value.decode()

@@ -367,6 +367,51 @@ int32_t rt_trace_family(rt_context* ctx, int32_t precision, int32_t traversal);
 rt_status rt_occluded(rt_context* ctx, const rt_trace_params* params, const double* rays, int64_t nrays,
                       uint8_t* out_occluded, void* stream);
 
+/* ---- radiance queries: path-traced radiance along caller-given rays (probes, lightmaps, gathers, relighting) ----
+ *
+ * out_rgb[i] = the mean over samples s in [first_sample, first_sample + spp) of camera::ray_color(ray_i, world,
+ * max_depth, light) (camera.h:193-241): what rt_render_tiles computes per pixel, without the camera. No reference
+ * counterpart as an entry point: the reference reaches ray_color through camera::render alone.
+ *
+ * rays: rt_trace_rays' format (nrays x 8 doubles, o[3], d[3] not normalised, time, tmax), so rt_camera_rays' output
+ * and existing ray buffers work unchanged. RT_PREC_F32 rounds o, d and time to float once. tmax is not read: the first
+ * segment runs over interval(0.001, inf) like every other (camera.h:198). A finite time is the ray time of every
+ * sample; a NaN time makes each sample draw its own as camera::generate_ray does, so a moving-sphere scene is
+ * motion-blurred per sample like a render.
+ * out_rgb: nrays x 3 floats (RT_PREC_F32) or doubles (RT_PREC_F64).
+ *
+ * Keys: the path of sample s of ray i is keyed (seed, pixel = ray_base + i, sample = s) and draws the counter-RNG
+ * dimensions a render's path with that key draws, except 0 and 1 (the pixel jitter), which are never drawn, and 2 (the
+ * ray time), drawn only for a NaN time. So ray i with a NaN time equals pixel ray_base + i of an N x 1 image rendered
+ * by rt_render_tiles through a perspective camera with pos = o_i, dir = d_i, focal_length = 1 and a zero viewport,
+ * with the same seed, spp, first_sample and max_depth -- up to the grouping of the sum over the samples, which
+ * follows the item layout (samples_per_item). With samples_per_item given, a ray's value depends on its key and
+ * nothing else: a batch split over several calls with matching ray_base gives bit-identical values.
+ *
+ * The kernel is the persistent path kernel a perspective render of the scene takes (family, shade form, LDS use),
+ * in its form that reads the batch; there is no wavefront schedule (no segments_per_launch) for it. */
+typedef struct rt_radiance_params {
+  uint64_t seed;
+  int32_t spp, first_sample; /* samples [first_sample, first_sample + spp) of every ray, spp >= 1; a negative
+                                first_sample counts as 0 */
+  int32_t max_depth;         /* 0: every ray is black (camera.h:194-195) */
+  int32_t precision;         /* rt_precision */
+  int32_t traversal;         /* rt_traversal */
+  int32_t samples_per_item;  /* as rt_render_params: 0 = automatic */
+  uint32_t ray_base;         /* ray i is keyed as pixel ray_base + i */
+  int32_t on_device;         /* 1: rays and out_rgb are device pointers, the call is stream-ordered */
+} rt_radiance_params;
+/* RT_ERR_INVALID_ARGUMENT: a null pointer, nrays < 0 or >= 2^31 (the item planner's limit for one call, whatever
+ * spp), ray_base + nrays > 2^32, spp < 1, max_depth < 0, an unknown precision or traversal, device pointers
+ * (on_device = 1) not aligned to 16 bytes; RT_ERR_NO_SCENE; RT_ERR_UNSUPPORTED: a family a development build omits.
+ * On an error nothing is launched and out_rgb is not written. nrays == 0 launches nothing. Adds nrays * spp to
+ * rt_counters.samples, the traced segments to segments and its launches (a path launch and a resolve per chunk pass)
+ * to launches; chunk passes and the partial-sum budget are a render's; with on_device = 1 the call joins the
+ * context's outstanding work exactly as a device-output render does (its launches stay on `stream`: consecutive
+ * batches do not overlap as consecutive frames do). */
+rt_status rt_radiance(rt_context* ctx, const rt_radiance_params* params, const double* rays, int64_t nrays,
+                      void* out_rgb, void* stream);
+
 /* ---- camera rays and feature buffers (AOVs): what a frame's pixels see first ----
  *
  * rt_camera_rays writes the rays camera::generate_ray (camera.h:244-293) draws for a render, in rt_trace_rays'
