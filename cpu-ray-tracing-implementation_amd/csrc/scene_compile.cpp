@@ -22,7 +22,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <functional>
 #include <limits>
 #include <new>
 #include <stdexcept>
@@ -136,6 +135,100 @@ void join_lin(Item& dst, const std::vector<Item>& items) {
   }
 }
 
+// What a tree is built over: the items' boxes and box centres, and the order a build leaves them in.
+struct BuildSet {
+  std::vector<Box> box;
+  std::vector<double> cen;  // three per item
+  std::vector<size_t> order;
+  explicit BuildSet(const std::vector<Item>& items) : box(items.size()), cen(3 * items.size()), order(items.size()) {
+    for (size_t i = 0; i < items.size(); i++) {
+      box[i] = items[i].box;
+      for (int k = 0; k < 3; k++) cen[3 * i + k] = items[i].box.center(k);
+      order[i] = i;
+    }
+  }
+  // the bounds of order[b, e) and of its centres; returns the axis of the largest centroid extent
+  int bounds(size_t b, size_t e, Box& all, Box& cb) const {
+    for (size_t i = b; i < e; i++) {
+      all.grow(box[order[i]]);
+      cb.grow(&cen[3 * order[i]]);
+    }
+    int axis = 0;
+    for (int k = 1; k < 3; k++)
+      if (cb.hi[k] - cb.lo[k] > cb.hi[axis] - cb.lo[axis]) axis = k;
+    return axis;
+  }
+};
+
+// The binned SAH split both tree builders use: `bins` equal bins between the centroid bounds cb on every axis of
+// the set `axes` (bit k: axis k) that has an extent, the planes between bins in ascending order, the cost
+// count * area of either side, and the first plane of least cost (strict <, axes ascending). axis < 0: no plane
+// has items on both sides.
+constexpr int kMaxBins = 32;
+struct Split {
+  int axis = -1, bin = 0;  // items of bins below `bin` go left
+  double cost = kInf;
+};
+inline int bin_of(const BuildSet& s, size_t item, int axis, const Box& cb, int bins) {
+  const double extent = cb.hi[axis] - cb.lo[axis];
+  return std::min(bins - 1, std::max(0, (int)((s.cen[3 * item + axis] - cb.lo[axis]) / extent * bins)));
+}
+Split sah_split(const BuildSet& s, size_t b, size_t e, const Box& cb, int bins, unsigned axes) {
+  Split best;
+  for (int ax = 0; ax < 3; ax++) {
+    if (!(axes >> ax & 1u) || !(cb.hi[ax] - cb.lo[ax] > 0)) continue;
+    Box bin_box[kMaxBins];
+    size_t bin_cnt[kMaxBins] = {};
+    for (size_t i = b; i < e; i++) {
+      const int k = bin_of(s, s.order[i], ax, cb, bins);
+      bin_cnt[k]++;
+      bin_box[k].grow(s.box[s.order[i]]);
+    }
+    Box rb[kMaxBins], acc;  // rb[k], rc[k]: bins k and above
+    size_t rc[kMaxBins] = {}, cnt = 0;
+    for (int k = bins - 1; k > 0; k--) {
+      acc.grow(bin_box[k]);
+      cnt += bin_cnt[k];
+      rb[k] = acc;
+      rc[k] = cnt;
+    }
+    Box lb;
+    size_t lc = 0;
+    for (int k = 1; k < bins; k++) {
+      lb.grow(bin_box[k - 1]);
+      lc += bin_cnt[k - 1];
+      if (!lc || !rc[k]) continue;
+      const double cost = lb.area() * (double)lc + rb[k].area() * (double)rc[k];
+      if (cost < best.cost) best = {ax, k, cost};
+    }
+  }
+  return best;
+}
+// Reorders order[b, e) by the split and returns where the right side begins; without a split that separates the
+// range, about the median along the split's axis (or, with no split at all, along `axis`).
+size_t partition_by_split(BuildSet& s, size_t b, size_t e, const Box& cb, int bins, const Split& sp, int axis) {
+  const auto first = s.order.begin() + (long)b, last = s.order.begin() + (long)e;
+  if (sp.axis >= 0) {
+    axis = sp.axis;
+    const auto it = std::partition(first, last, [&](size_t p) { return bin_of(s, p, axis, cb, bins) < sp.bin; });
+    const size_t mid = (size_t)(it - s.order.begin());
+    if (mid > b && mid < e) return mid;
+  }
+  const size_t mid = b + (e - b) / 2;
+  std::nth_element(first, s.order.begin() + (long)mid, last,
+                   [&](size_t x, size_t y) { return s.cen[3 * x + axis] < s.cen[3 * y + axis]; });
+  return mid;
+}
+
+// The flat program's records in double (rt_scene.h). quads / nq: the quad groups without the faces of rooms;
+// quads_all / nq_all: with them (a blob that keeps its walls as quads), in the same order.
+struct FlatProgram {
+  std::vector<FlatQuadT<double>> quads, quads_all;
+  uint32_t nq[3] = {0, 0, 0}, nq_all[3] = {0, 0, 0};
+  std::vector<FlatBoxT<double>> boxes;
+  std::vector<FlatRoomT<double>> rooms;
+};
+
 class Compiler {
  public:
   explicit Compiler(const rt_scene_desc* d) : d_(d) {}
@@ -181,37 +274,80 @@ class Compiler {
     if (m < 0 || m >= d_->num_materials) return fail("primitive without a valid material");
     return true;
   }
+  bool check_children(const rt_object& o, const char* what) {
+    if (o.first_child < 0 || o.child_count < 0 || o.first_child + o.child_count > d_->num_children)
+      return fail(std::string(what) + " child range out of bounds");
+    return true;
+  }
   static bool is_wrapper(int kind) { return kind >= RT_OBJ_TRANSLATE && kind <= RT_OBJ_ROTATE_Z; }
   static Op op_of(const rt_object& o) {
     if (o.kind == RT_OBJ_TRANSLATE) return {0, o.a[0], o.a[1], o.a[2]};
     return {o.kind - RT_OBJ_ROTATE_X + 1, o.s0, o.s1, 0.0};
   }
 
+  // The translate / rotate wrappers from w down to the first object that is none (returned; nullptr after a
+  // failure), as ops, and after the wrappers of `chain` as chain2.
+  const rt_object* unwrap(const rt_object* w, const std::vector<Op>& chain, std::vector<Op>& ops, std::vector<Op>& chain2) {
+    while (w && is_wrapper(w->kind)) {
+      if ((int)(chain.size() + ops.size()) >= kMaxChain) {
+        fail("more than " + std::to_string(kMaxChain) + " nested translate/rotate wrappers (or a cycle)");
+        return nullptr;
+      }
+      ops.push_back(op_of(*w));
+      w = obj(w->child);
+    }
+    chain2 = chain;
+    chain2.insert(chain2.end(), ops.begin(), ops.end());
+    return w;
+  }
   Item prim_item(const rt_object& o);
   void gather(int idx, const std::vector<Op>& chain, std::vector<Item>& out, bool ordered_ctx);
   Item container(std::vector<Item>& items, bool ordered);
   Item list_of(const std::vector<Item>& items);
-  Item bvh(std::vector<Item>& items, size_t b, size_t e, int depth);
+  Item bvh(std::vector<Item>& items);
+  Item bvh_range(const std::vector<Item>& items, BuildSet& s, size_t b, size_t e, int depth);
   int make_instance(const std::vector<Op>& chain, uint32_t blas);
   LinRec<double> lin_record(uint32_t op) const;
-  bool flat_program(const std::vector<uint32_t>& lin, std::vector<FlatQuadT<double>>& quads, uint32_t nq[3],
-                    std::vector<FlatBoxT<double>>& boxes, std::vector<FlatRoomT<double>>& rooms,
-                    std::vector<FlatQuadT<double>>& quads_all, uint32_t nq_all[3]);
+  bool flat_program(const std::vector<uint32_t>& lin, FlatProgram& fp);
+  bool compile_materials();
+  bool build_root(std::vector<Item>& top, Item& root);
+  void pack_blobs(CompiledScene* out, const std::vector<LinRec<double>>& linear, const FlatProgram* flat) const;
+  void id_tables(CompiledScene* out) const;
   bool wide_bvh(const std::vector<Item>& prims, CompiledScene* out);
   bool box_of_quads(const std::vector<Item>& prims, double lo[3], double hi[3]) const;
   std::vector<int> aligned_;  // per quad: 1 + perm for axis-aligned quads, 0 otherwise
   std::vector<double> qu_, qv_;  // per quad: u[U], v[V] (aligned quads)
   // per quad / sphere / triangle / volume record: the descriptor object it was compiled from (CompiledScene::ids)
   std::vector<int32_t> quad_obj_, sphere_obj_, tri_obj_, vol_obj_;
+  // axis-aligned quad i as a LinRec and the light hold it: q[A], q[U], q[V], 1/u[U], 1/v[V], u[U], v[V]
+  void aligned_quad(size_t i, double* f) const {
+    const int* ax = kPermAxes[aligned_[i] - 1];
+    for (int k = 0; k < 3; k++) f[k] = quads_[i].q[ax[k]];
+    f[3] = 1.0 / qu_[i];
+    f[4] = 1.0 / qv_[i];
+    f[5] = qu_[i];
+    f[6] = qv_[i];
+  }
+  void truncate_quads(size_t n) {  // the quad records and what is kept beside them
+    quads_.resize(n);
+    quad_obj_.resize(n);
+    aligned_.resize(n);
+    qu_.resize(n);
+    qv_.resize(n);
+  }
+  void copy_quad(size_t i, int32_t obj) {  // quad record i once more, for the descriptor object obj
+    quads_.push_back(quads_[i]);
+    quad_obj_.push_back(obj);
+    aligned_.push_back(aligned_[i]);
+    qu_.push_back(qu_[i]);
+    qv_.push_back(qv_[i]);
+  }
   void light_from(int idx);
 };
 
 Item Compiler::prim_item(const rt_object& o) {
   Item it{};
   const int32_t oi = (int32_t)(&o - d_->objects);
-  it.need = 0;
-  it.depth = 0;
-  it.volume = false;
   if (!check_mat(o.material)) return it;
   if (o.kind == RT_OBJ_QUAD) {  // quad.h:9-23
     Quad<double> q{};
@@ -314,7 +450,12 @@ int Compiler::make_instance(const std::vector<Op>& chain, uint32_t blas) {
   }
   Instance<double> in{};
   in.nops = (int)chain.size();
-  for (size_t k = 0; k < chain.size(); k++) in.op[k] = {chain[k].x, chain[k].y, chain[k].z, chain[k].kind};
+  for (size_t k = 0; k < chain.size(); k++) {  // field by field: a temporary XOp's padding would be undefined bytes
+    in.op[k].x = chain[k].x;
+    in.op[k].y = chain[k].y;
+    in.op[k].z = chain[k].z;
+    in.op[k].kind = chain[k].kind;
+  }
   in.blas = blas;
   insts_.push_back(in);
   return (int)insts_.size() - 1;
@@ -323,9 +464,6 @@ int Compiler::make_instance(const std::vector<Op>& chain, uint32_t blas) {
 Item Compiler::list_of(const std::vector<Item>& items) {
   Item it{};
   it.entry = mk(E_LIST, (uint32_t)refs_.size());
-  it.need = 0;
-  it.depth = 0;
-  it.volume = false;
   for (const Item& m : items) {
     refs_.push_back(m.entry);
     it.box.grow(m.box);
@@ -339,80 +477,38 @@ Item Compiler::list_of(const std::vector<Item>& items) {
   return it;
 }
 
-Item Compiler::bvh(std::vector<Item>& items, size_t b, size_t e, int depth) {
-  size_t n = e - b;
-  if (n == 1) return items[b];
+// A SAH BVH over the items (binary nodes, leaves of up to kLeafMax items as lists): 16 bins on the largest centroid
+// axis. Leaves the items in the tree's order.
+Item Compiler::bvh(std::vector<Item>& items) {
+  BuildSet s(items);
+  const Item root = bvh_range(items, s, 0, items.size(), 0);
+  std::vector<Item> sorted;
+  sorted.reserve(items.size());
+  for (size_t i : s.order) sorted.push_back(std::move(items[i]));
+  items.swap(sorted);
+  return root;
+}
+
+Item Compiler::bvh_range(const std::vector<Item>& items, BuildSet& s, size_t b, size_t e, int depth) {
+  const size_t n = e - b;
+  if (n == 1) return items[s.order[b]];
+  auto leaf = [&]() {
+    std::vector<Item> members;
+    for (size_t i = b; i < e; i++) members.push_back(items[s.order[i]]);
+    return list_of(members);
+  };
   Box bounds, cb;
-  for (size_t i = b; i < e; i++) {
-    bounds.grow(items[i].box);
-    double c[3] = {items[i].box.center(0), items[i].box.center(1), items[i].box.center(2)};
-    cb.grow(c);
-  }
-  if (n <= (size_t)kLeafMax && depth > 0) {
-    std::vector<Item> leaf(items.begin() + (long)b, items.begin() + (long)e);
-    return list_of(leaf);
-  }
-  // binned SAH over the largest centroid axis
-  int axis = 0;
-  for (int k = 1; k < 3; k++)
-    if (cb.hi[k] - cb.lo[k] > cb.hi[axis] - cb.lo[axis]) axis = k;
-  size_t mid = b + n / 2;
-  double extent = cb.hi[axis] - cb.lo[axis];
-  bool split_found = false;
-  if (extent > 0 && depth < kMaxBvhDepth - 4) {
-    constexpr int kBins = 16;
-    Box bin_box[kBins];
-    size_t bin_cnt[kBins] = {};
-    auto bin_of = [&](const Item& it) {
-      int k = (int)((it.box.center(axis) - cb.lo[axis]) / extent * kBins);
-      return std::min(kBins - 1, std::max(0, k));
-    };
-    for (size_t i = b; i < e; i++) {
-      int k = bin_of(items[i]);
-      bin_cnt[k]++;
-      bin_box[k].grow(items[i].box);
-    }
-    double best = kInf;
-    int best_k = -1;
-    for (int s = 1; s < kBins; s++) {
-      Box lb, rb;
-      size_t lc = 0, rc = 0;
-      for (int k = 0; k < s; k++) {
-        lb.grow(bin_box[k]);
-        lc += bin_cnt[k];
-      }
-      for (int k = s; k < kBins; k++) {
-        rb.grow(bin_box[k]);
-        rc += bin_cnt[k];
-      }
-      if (!lc || !rc) continue;
-      double cost = lb.area() * (double)lc + rb.area() * (double)rc;
-      if (cost < best) {
-        best = cost;
-        best_k = s;
-      }
-    }
-    if (best_k > 0) {
-      double leaf_cost = bounds.area() * (double)n;
-      if (n <= (size_t)kLeafMax && best >= leaf_cost) {
-        std::vector<Item> leaf(items.begin() + (long)b, items.begin() + (long)e);
-        return list_of(leaf);
-      }
-      auto it = std::partition(items.begin() + (long)b, items.begin() + (long)e,
-                               [&](const Item& x) { return bin_of(x) < best_k; });
-      mid = (size_t)(it - items.begin());
-      split_found = mid > b && mid < e;
-    }
-  }
-  if (!split_found) {
-    mid = b + n / 2;
-    std::nth_element(items.begin() + (long)b, items.begin() + (long)mid, items.begin() + (long)e,
-                     [&](const Item& x, const Item& y) { return x.box.center(axis) < y.box.center(axis); });
-  }
+  const int axis = s.bounds(b, e, bounds, cb);
+  if (n <= (size_t)kLeafMax && depth > 0) return leaf();
+  constexpr int kBins = 16;
+  Split sp;
+  if (cb.hi[axis] - cb.lo[axis] > 0 && depth < kMaxBvhDepth - 4) sp = sah_split(s, b, e, cb, kBins, 1u << axis);
+  if (sp.axis >= 0 && n <= (size_t)kLeafMax && sp.cost >= bounds.area() * (double)n) return leaf();
+  const size_t mid = partition_by_split(s, b, e, cb, kBins, sp, axis);
   size_t node_idx = nodes_.size();
   nodes_.emplace_back();
-  Item l = bvh(items, b, mid, depth + 1);
-  Item r = bvh(items, mid, e, depth + 1);
+  Item l = bvh_range(items, s, b, mid, depth + 1);
+  Item r = bvh_range(items, s, mid, e, depth + 1);
   Node<double>& nd = nodes_[node_idx];
   for (int k = 0; k < 3; k++) {
     nd.lo[0][k] = l.box.lo[k];
@@ -439,7 +535,7 @@ Item Compiler::container(std::vector<Item>& items, bool ordered) {
   if (ordered || has_volume || items.size() <= (size_t)kSmallList) return list_of(items);
   Item lin_src;
   join_lin(lin_src, items);  // reference (gather) order, before the BVH build reorders
-  Item it = bvh(items, 0, items.size(), 0);
+  Item it = bvh(items);
   it.lin = std::move(lin_src.lin);
   it.lin_ok = lin_src.lin_ok;
   return it;
@@ -460,17 +556,11 @@ void Compiler::gather(int idx, const std::vector<Op>& chain, std::vector<Item>& 
       out.push_back(prim_item(*o));
       break;
     case RT_OBJ_LIST:  // spliced in order: closest-hit over nested lists is the same scan
-      if (o->first_child < 0 || o->child_count < 0 || o->first_child + o->child_count > d_->num_children) {
-        fail("list child range out of bounds");
-        break;
-      }
+      if (!check_children(*o, "list")) break;
       for (int k = 0; k < o->child_count; k++) gather(d_->children[o->first_child + k], chain, out, ordered_ctx);
       break;
     case RT_OBJ_BVH: {
-      if (o->first_child < 0 || o->child_count < 0 || o->first_child + o->child_count > d_->num_children) {
-        fail("bvh child range out of bounds");
-        break;
-      }
+      if (!check_children(*o, "bvh")) break;
       std::vector<Item> sub;
       for (int k = 0; k < o->child_count; k++) gather(d_->children[o->first_child + k], chain, sub, false);
       if (!ok_) break;
@@ -485,19 +575,9 @@ void Compiler::gather(int idx, const std::vector<Op>& chain, std::vector<Item>& 
     case RT_OBJ_ROTATE_X:
     case RT_OBJ_ROTATE_Y:
     case RT_OBJ_ROTATE_Z: {
-      std::vector<Op> ops;
-      const rt_object* w = o;
-      while (w && is_wrapper(w->kind)) {
-        if ((int)(chain.size() + ops.size()) >= kMaxChain) {
-          fail("more than " + std::to_string(kMaxChain) + " nested translate/rotate wrappers (or a cycle)");
-          return;
-        }
-        ops.push_back(op_of(*w));
-        w = obj(w->child);
-      }
+      std::vector<Op> ops, chain2;
+      const rt_object* w = unwrap(o, chain, ops, chain2);
       if (!w) break;
-      std::vector<Op> chain2 = chain;
-      chain2.insert(chain2.end(), ops.begin(), ops.end());
       std::vector<Item> sub;
       gather((int)(w - d_->objects), chain2, sub, false);
       if (!ok_) break;
@@ -528,19 +608,9 @@ void Compiler::gather(int idx, const std::vector<Op>& chain, std::vector<Item>& 
         fail("volume without a phase material");
         break;
       }
-      std::vector<Op> ops;
-      const rt_object* w = obj(o->child);
-      while (w && is_wrapper(w->kind)) {
-        if ((int)(chain.size() + ops.size()) >= kMaxChain) {
-          fail("more than " + std::to_string(kMaxChain) + " nested translate/rotate wrappers (or a cycle)");
-          return;
-        }
-        ops.push_back(op_of(*w));
-        w = obj(w->child);
-      }
+      std::vector<Op> ops, chain2;
+      const rt_object* w = unwrap(obj(o->child), chain, ops, chain2);
       if (!w) break;
-      std::vector<Op> chain2 = chain;
-      chain2.insert(chain2.end(), ops.begin(), ops.end());
       std::vector<Item> prims;
       gather((int)(w - d_->objects), chain2, prims, true);
       if (!ok_) break;
@@ -563,8 +633,6 @@ void Compiler::gather(int idx, const std::vector<Op>& chain, std::vector<Item>& 
       Item it{};
       it.entry = mk(E_VOLUME, (uint32_t)vols_.size() - 1);
       it.box = box_to_parent(bl.box, ops);
-      it.need = 0;
-      it.depth = 0;
       it.volume = true;
       it.lin = {it.entry};
       out.push_back(it);
@@ -586,28 +654,16 @@ void Compiler::light_from(int idx) {
   if (!o) return;
   if (o->kind == RT_OBJ_QUAD) {  // quad::pdf_value / random (quad.h:66-78)
     size_t before = quads_.size();
-    Item it = prim_item(*o);
-    (void)it;
+    prim_item(*o);
     if (!ok_) return;
     light_.kind = L_QUAD;
     light_.quad = quads_.back();
     if (aligned_.back()) {
-      const int* ax = kPermAxes[aligned_.back() - 1];
       light_.aligned = aligned_.back();
-      light_.af[0] = light_.quad.q[ax[0]];
-      light_.af[1] = light_.quad.q[ax[1]];
-      light_.af[2] = light_.quad.q[ax[2]];
-      light_.af[3] = 1.0 / qu_.back();
-      light_.af[4] = 1.0 / qv_.back();
-      light_.af[5] = qu_.back();
-      light_.af[6] = qv_.back();
+      aligned_quad(before, light_.af);
       light_.af[7] = 1.0 / light_.quad.area;  // fp64 light_pdf_aligned
     }
-    quads_.resize(before);
-    quad_obj_.resize(before);
-    aligned_.resize(before);
-    qu_.resize(before);
-    qv_.resize(before);
+    truncate_quads(before);
     for (int k = 0; k < 3; k++) {
       light_.u[k] = o->b[k];
       light_.v[k] = o->c[k];
@@ -621,11 +677,28 @@ void Compiler::light_from(int idx) {
   }
 }
 
+// Every array of a blob starts on a 256-byte boundary, and the blob ends on one.
+inline size_t pad256(std::vector<unsigned char>& blob) {
+  blob.resize((blob.size() + 255) & ~size_t(255));
+  return blob.size();
+}
 template <class T>
-size_t append(std::vector<unsigned char>& blob, const std::vector<T>& v) {
-  size_t off = (blob.size() + 255) & ~size_t(255);
+void append_bytes(std::vector<unsigned char>& blob, const std::vector<T>& v) {
+  const size_t off = blob.size();
   blob.resize(off + v.size() * sizeof(T));
   if (!v.empty()) std::memcpy(blob.data() + off, v.data(), v.size() * sizeof(T));
+}
+template <class T>
+size_t append(std::vector<unsigned char>& blob, const std::vector<T>& v) {
+  const size_t off = pad256(blob);
+  append_bytes(blob, v);
+  return off;
+}
+// two arrays as one: b's records start where a's end (rt_types.h flat_rooms); returns a's offset
+template <class A, class B>
+size_t append_pair(std::vector<unsigned char>& blob, const std::vector<A>& a, const std::vector<B>& b) {
+  const size_t off = append(blob, a);
+  append_bytes(blob, b);
   return off;
 }
 
@@ -794,6 +867,28 @@ Light<float> to32(const Light<double>& l) {
   for (int k = 0; k < 8; k++) r.af[k] = (float)l.af[k];
   return r;
 }
+FlatQuadT<float> to32(const FlatQuadT<double>& q) {
+  return {(float)q.plane, (float)q.lo_u, (float)q.lo_w, (float)q.inv_u, (float)q.inv_w, q.e, q.inst, q.nm};
+}
+FlatRoomT<float> to32(const FlatRoomT<double>& b) {
+  FlatRoomT<float> r{};
+  cvt3(r.lo, b.lo);
+  cvt3(r.hi, b.hi);
+  r.inst = b.inst;
+  r.present = b.present;
+  for (int f = 0; f < 6; f++) r.e[f] = b.e[f], r.nm[f] = b.nm[f];
+  return r;
+}
+FlatBoxT<float> to32(const FlatBoxT<double>& b) {
+  FlatBoxT<float> r{};
+  cvt3(r.lo, b.lo);
+  cvt3(r.hi, b.hi);
+  r.inst = b.inst;
+  r.mat = b.mat;
+  for (int f = 0; f < 6; f++) r.face[f] = b.face[f];
+  r.neg = b.neg;
+  return r;
+}
 template <class T>
 auto map32(const std::vector<T>& v) {
   std::vector<decltype(to32(v[0]))> r;
@@ -826,8 +921,7 @@ SceneHeader pack(std::vector<unsigned char>& blob, const std::vector<Q>& q, cons
   h.n_texdata = texdata.size();
   h.off_images = append(blob, images);
   h.n_images = images.size();
-  blob.resize((blob.size() + 255) & ~size_t(255));
-  h.bytes = blob.size();
+  h.bytes = pad256(blob);
   h.n_quads = (uint32_t)q.size();
   h.n_spheres = (uint32_t)s.size();
   h.n_tris = (uint32_t)t.size();
@@ -846,8 +940,6 @@ SceneHeader pack(std::vector<unsigned char>& blob, const std::vector<Q>& q, cons
   h.light_aligned = light.aligned;
   return h;
 }
-
-// perm -> (A, U, V): the plane axis and the axes of u and v (rt_scene.h LinRec)
 
 LinRec<double> Compiler::lin_record(uint32_t op) const {
   LinRec<double> r{};
@@ -868,15 +960,8 @@ LinRec<double> Compiler::lin_record(uint32_t op) const {
   if (ty == E_QUAD) {
     const Quad<double>& q = quads_[i];
     if (aligned_[i]) {
-      const int* ax = kPermAxes[aligned_[i] - 1];
       r.aux = (uint32_t)aligned_[i];
-      r.f[0] = q.q[ax[0]];
-      r.f[1] = q.q[ax[1]];
-      r.f[2] = q.q[ax[2]];
-      r.f[3] = 1.0 / qu_[i];
-      r.f[4] = 1.0 / qv_[i];
-      r.f[5] = qu_[i];
-      r.f[6] = qv_[i];
+      aligned_quad(i, r.f);
     } else {
       for (int k = 0; k < 3; k++) {
         r.f[k] = q.n[k];
@@ -908,11 +993,7 @@ LinRec<double> Compiler::lin_record(uint32_t op) const {
 // The flat program of rt_scene.h: the linear program's ops are all axis-aligned quads, at world
 // level or in translate-only instances. Returns false (no flat program) for anything else. The
 // records come out in double (the fp64 blob) and are rounded once for the fp32 blob (flat32).
-// quads / nq: the quad groups without the faces of rooms; quads_all / nq_all: with them (a blob that keeps
-// its walls as quads), in the same order.
-bool Compiler::flat_program(const std::vector<uint32_t>& lin, std::vector<FlatQuadT<double>>& quads, uint32_t nq[3],
-                            std::vector<FlatBoxT<double>>& boxes, std::vector<FlatRoomT<double>>& rooms,
-                            std::vector<FlatQuadT<double>>& quads_all, uint32_t nq_all[3]) {
+bool Compiler::flat_program(const std::vector<uint32_t>& lin, FlatProgram& fp) {
   struct Q {
     uint32_t e;
     int32_t inst;
@@ -1020,7 +1101,7 @@ bool Compiler::flat_program(const std::vector<uint32_t>& lin, std::vector<FlatQu
           r.nm[f] = nm_of(pend[face[f]].q);
           pend[face[f]].in_room = true;
         }
-        rooms.push_back(r);
+        fp.rooms.push_back(r);
       }
     }
   };
@@ -1042,8 +1123,9 @@ bool Compiler::flat_program(const std::vector<uint32_t>& lin, std::vector<FlatQu
       if (cnt[k] != 2 || !(lo[k] < hi[k])) return false;
     int seen[6] = {0, 0, 0, 0, 0, 0};
     for (const Q& q : qs) {  // each face spans the box exactly in its two in-plane axes
-      const double u0 = std::min(q.lo_u, q.lo_u + q.len_u), u1 = std::max(q.lo_u, q.lo_u + q.len_u);
-      const double w0 = std::min(q.lo_w, q.lo_w + q.len_w), w1 = std::max(q.lo_w, q.lo_w + q.len_w);
+      double u0, u1, w0, w1;
+      extent(q, q.U, u0, u1);
+      extent(q, q.W, w0, w1);
       if (u0 != lo[q.U] || u1 != hi[q.U] || w0 != lo[q.W] || w1 != hi[q.W]) return false;
       const int f = 2 * q.A + (q.plane == hi[q.A] ? 1 : 0);
       if (seen[f]++) return false;
@@ -1060,11 +1142,7 @@ bool Compiler::flat_program(const std::vector<uint32_t>& lin, std::vector<FlatQu
   };
   const size_t quads_before = quads_.size();
   auto undo = [&]() {
-    quads_.resize(quads_before);
-    quad_obj_.resize(quads_before);
-    aligned_.resize(quads_before);
-    qu_.resize(quads_before);
-    qv_.resize(quads_before);
+    truncate_quads(quads_before);
     return false;
   };
   for (size_t k = 0; k < lin.size(); k++) {
@@ -1096,23 +1174,13 @@ bool Compiler::flat_program(const std::vector<uint32_t>& lin, std::vector<FlatQu
     if (as_box(qs, off, b)) {
       // the faces get copies of their quad records at an 8-aligned index, face j at base + j:
       // a ray leaving the box knows from its entry which slab plane it starts on (trace_flat)
-      while (quads_.size() % 8) {
-        quads_.push_back(quads_[0]);
-        quad_obj_.push_back(-1);  // padding: no traversal returns it
-        aligned_.push_back(aligned_[0]);
-        qu_.push_back(qu_[0]);
-        qv_.push_back(qv_[0]);
-      }
+      while (quads_.size() % 8) copy_quad(0, -1);  // padding: no traversal returns it
       for (int f = 0; f < 6; f++) {
         const uint32_t i = epay(b.face[f]);
-        quads_.push_back(quads_[i]);
-        quad_obj_.push_back(quad_obj_[i]);  // a face copy names the descriptor quad it came from
-        aligned_.push_back(aligned_[i]);
-        qu_.push_back(qu_[i]);
-        qv_.push_back(qv_[i]);
+        copy_quad(i, quad_obj_[i]);  // a face copy names the descriptor quad it came from
         b.face[f] = mk(E_QUAD, (uint32_t)quads_.size() - 1);
       }
-      boxes.push_back(b);
+      fp.boxes.push_back(b);
     } else {
       for (const Q& q : qs) pend.push_back({q, {off[0], off[1], off[2]}, pools, false});
       pools++;
@@ -1120,13 +1188,11 @@ bool Compiler::flat_program(const std::vector<uint32_t>& lin, std::vector<FlatQu
   }
   for (int p = 0; p < pools; p++) find_rooms(p);
   for (const Pending& p : pend) add_quad(p.q, p.off, p.in_room);
-  quads.clear();
-  quads_all.clear();
   for (int a = 0; a < 3; a++) {
-    nq[a] = (uint32_t)grp[a].size();
-    quads.insert(quads.end(), grp[a].begin(), grp[a].end());
-    nq_all[a] = (uint32_t)grp_all[a].size();
-    quads_all.insert(quads_all.end(), grp_all[a].begin(), grp_all[a].end());
+    fp.nq[a] = (uint32_t)grp[a].size();
+    fp.quads.insert(fp.quads.end(), grp[a].begin(), grp[a].end());
+    fp.nq_all[a] = (uint32_t)grp_all[a].size();
+    fp.quads_all.insert(fp.quads_all.end(), grp_all[a].begin(), grp_all[a].end());
   }
   return true;
 }
@@ -1160,128 +1226,44 @@ bool Compiler::box_of_quads(const std::vector<Item>& prims, double lo[3], double
   return faces == 63;
 }
 
+// ---------------------------------------------------------------- the wide BVH
 // The wide BVH of rt_scene.h (fp32 kernels) over world-level primitives: a binned SAH binary
 // tree, collapsed into 4-wide nodes by repeatedly opening the child of largest surface area.
 // Leaves hold their primitives' records in leaf order (no reference list). Closest hits do not
 // depend on the tree except on exact-t ties, as for the binary BVH.
-bool Compiler::wide_bvh(const std::vector<Item>& all, CompiledScene* out) {
-  // Primitives whose box covers a large part of the scene (the RTOW ground sphere, r = 1000) would
-  // sit in a leaf that almost every ray reaches, beside leaves of small primitives whose tests
-  // diverge from it. They are tested first, by every lane alike, before the tree (whose traversal
-  // then starts with their hit distance as its bound).
-  std::vector<Item> prims, big;
-  {
-    Box scene;
-    for (const Item& it : all) scene.grow(it.box);
-    const double sa = scene.area();
-    for (const Item& it : all)
-      (sa > 0 && it.box.area() > 0.25 * sa && big.size() < 4 ? big : prims).push_back(it);
-    if (prims.size() < 2) {
-      prims = all;
-      big.clear();
-    }
-  }
-  struct BN {
-    Box box;
-    int left = -1, right = -1;  // children (inner), or -1
-    size_t first = 0, count = 0;  // primitive range (leaf)
-  };
-  std::vector<BN> bn;
-  std::vector<size_t> order(prims.size());
-  for (size_t i = 0; i < order.size(); i++) order[i] = i;
-  std::vector<double> cen(prims.size() * 3);
-  for (size_t i = 0; i < prims.size(); i++)
-    for (int k = 0; k < 3; k++) cen[3 * i + k] = prims[i].box.center(k);
-  // binary build, iterative (meshes are deep); SAH with a node traversal cost of 1 primitive test
+struct BinNode {
+  Box box;
+  int left = -1, right = -1;    // children (inner), or -1
+  size_t first = 0, count = 0;  // range of BuildSet::order (leaf)
+};
+
+// The binary tree over the set, iterative (meshes are deep); SAH with a node traversal cost of 1 primitive test.
+std::vector<BinNode> wide_binary_tree(BuildSet& s, bool all_spheres) {
   constexpr int kBins = 32;
   // leaves of up to kWLeafMax primitives, kWLeafMaxSpheres when all are spheres (a sphere test is
   // cheap next to a node visit; C3: leaves of 1/2/3/4/5/6/7/8 spheres 82.8/69.2/71.9/66.3/64.9/
   // 64.0/66.2/67.8 ms/frame; C4's triangles in HBM: 4 -> 742, 6 -> 817). A SAH leaf test on top
   // (node cost 1-8 primitive tests) was no better than the fixed sizes.
-  bool all_spheres = true;
-  for (const Item& it : prims) all_spheres = all_spheres && etype(it.entry) == E_SPHERE;
   size_t leaf_max = (size_t)(all_spheres ? kWLeafMaxSpheres : kWLeafMax);  // triangles: 3 (r03j C4 357.9 vs 362.7)
   if (const char* v = std::getenv("RT_DEV_WIDE_LEAF")) leaf_max = (size_t)std::max(1, std::min(8, std::atoi(v)));
   // split planes: binned SAH over all three axes (C4's triangles: 743 -> 458 ms/frame against the
   // largest centroid extent only), but the largest axis only for sphere trees (C3: 64.2 vs 65.1)
   int sah_axes = all_spheres ? 1 : 3;
   if (const char* v = std::getenv("RT_DEV_WIDE_AXES")) sah_axes = std::atoi(v);
-  bn.push_back(BN{});
-  bn[0].first = 0;
-  bn[0].count = prims.size();
+  std::vector<BinNode> bn(1);
+  bn[0].count = s.order.size();
   std::vector<int> todo{0};
   while (!todo.empty()) {
     const int ni = todo.back();
     todo.pop_back();
-    const size_t b = bn[(size_t)ni].first, n = bn[(size_t)ni].count, e = b + n;
-    Box bounds, cb;
-    for (size_t i = b; i < e; i++) {
-      bounds.grow(prims[order[i]].box);
-      cb.grow(&cen[3 * order[i]]);
-    }
-    bn[(size_t)ni].box = bounds;
-    if (n <= leaf_max) continue;  // a leaf: one 4-wide node's worth of tests
-    int axis = 0;
-    for (int k = 1; k < 3; k++)
-      if (cb.hi[k] - cb.lo[k] > cb.hi[axis] - cb.lo[axis]) axis = k;
-    size_t mid = b + n / 2;
-    bool split = false;
-    // binned SAH over every axis with a centroid extent (or the largest one only: sah_axes = 1)
-    double best = kInf;
-    int best_k = -1, best_axis = axis;
-    for (int ax = 0; ax < 3; ax++) {
-      if (sah_axes == 1 && ax != axis) continue;
-      const double extent = cb.hi[ax] - cb.lo[ax];
-      if (!(extent > 0)) continue;
-      Box bin_box[kBins];
-      size_t bin_cnt[kBins] = {};
-      for (size_t i = b; i < e; i++) {
-        const size_t p = order[i];
-        const int k = std::min(kBins - 1, std::max(0, (int)((cen[3 * p + ax] - cb.lo[ax]) / extent * kBins)));
-        bin_cnt[k]++;
-        bin_box[k].grow(prims[p].box);
-      }
-      Box rb[kBins];
-      size_t rc[kBins] = {};
-      Box acc;
-      size_t cnt = 0;
-      for (int k = kBins - 1; k > 0; k--) {
-        acc.grow(bin_box[k]);
-        cnt += bin_cnt[k];
-        rb[k] = acc;
-        rc[k] = cnt;
-      }
-      Box lb;
-      size_t lc = 0;
-      for (int k = 1; k < kBins; k++) {
-        lb.grow(bin_box[k - 1]);
-        lc += bin_cnt[k - 1];
-        if (!lc || !rc[k]) continue;
-        const double cost = lb.area() * (double)lc + rb[k].area() * (double)rc[k];
-        if (cost < best) {
-          best = cost;
-          best_k = k;
-          best_axis = ax;
-        }
-      }
-    }
-    if (best_k > 0) {
-      axis = best_axis;
-      const double extent = cb.hi[axis] - cb.lo[axis];
-      auto it = std::partition(order.begin() + (long)b, order.begin() + (long)e, [&](size_t p) {
-        return std::min(kBins - 1, std::max(0, (int)((cen[3 * p + axis] - cb.lo[axis]) / extent * kBins))) < best_k;
-      });
-      mid = (size_t)(it - order.begin());
-      split = mid > b && mid < e;
-    }
-    if (!split) {
-      mid = b + n / 2;
-      std::nth_element(order.begin() + (long)b, order.begin() + (long)mid, order.begin() + (long)e,
-                       [&](size_t x, size_t y) { return cen[3 * x + axis] < cen[3 * y + axis]; });
-    }
+    const size_t b = bn[(size_t)ni].first, e = b + bn[(size_t)ni].count;
+    Box cb;
+    const int axis = s.bounds(b, e, bn[(size_t)ni].box, cb);
+    if (e - b <= leaf_max) continue;  // a leaf: one 4-wide node's worth of tests
+    const Split sp = sah_split(s, b, e, cb, kBins, sah_axes == 1 ? 1u << axis : 7u);
+    const size_t mid = partition_by_split(s, b, e, cb, kBins, sp, axis);
     const int l = (int)bn.size(), r = l + 1;
-    bn.push_back(BN{});
-    bn.push_back(BN{});
+    bn.resize(bn.size() + 2);
     bn[(size_t)l].first = b;
     bn[(size_t)l].count = mid - b;
     bn[(size_t)r].first = mid;
@@ -1291,104 +1273,97 @@ bool Compiler::wide_bvh(const std::vector<Item>& all, CompiledScene* out) {
     todo.push_back(r);
     todo.push_back(l);
   }
+  return bn;
+}
 
-  // primitive records in leaf order
+// The 4-wide nodes and the primitive words (rt_scene.h WNode) of a binary tree.
+struct WideEmit {
+  const std::vector<Quad<double>>& quads;
+  const std::vector<Sphere<double>>& spheres;
+  const std::vector<Tri<double>>& tris;
+  const std::vector<Item>& prims;
+  const std::vector<size_t>& order;
+  const std::vector<BinNode>& bn;
   struct W4 {
     float x, y, z, w;
   };
-  std::vector<W4> words;
   // the same stream in double for the fp64 blob (fp64 rays over the same float boxes, rt_device.h
   // trace_wide): word for word, so the leaf codes serve both; the entry in the low bits of w
   struct W8 {
     double x, y, z, w;
   };
-  std::vector<W8> words64;
+  std::vector<WNode> wn = {};
+  std::vector<W4> words = {};  // primitive records in leaf order
+  std::vector<W8> words64 = {};
   uint32_t kinds = 0;
-  auto bits = [](uint32_t u) {
-    float f;
-    std::memcpy(&f, &u, 4);
-    return f;
-  };
-  auto bits64 = [](uint32_t u) {
-    const uint64_t v = u;
-    double f;
-    std::memcpy(&f, &v, 8);
-    return f;
-  };
-  auto put_prim = [&](uint32_t e) {  // the record of one primitive (rt_scene.h WNode)
+
+  void put(uint32_t e, const double* v, double w, bool entry) {
+    const uint64_t e64 = e;
+    float ef;
+    double ed;
+    std::memcpy(&ef, &e, 4);
+    std::memcpy(&ed, &e64, 8);
+    words.push_back({(float)v[0], (float)v[1], (float)v[2], entry ? ef : (float)w});
+    words64.push_back({v[0], v[1], v[2], entry ? ed : w});
+  }
+  bool put_prim(uint32_t e) {  // the record of one primitive
     const uint32_t ix = epay(e);
-    auto put = [&](const double* v, double w, bool entry) {
-      words.push_back({(float)v[0], (float)v[1], (float)v[2], entry ? bits(e) : (float)w});
-      words64.push_back({v[0], v[1], v[2], entry ? bits64(e) : w});
-    };
     if (etype(e) == E_SPHERE) {
-      const Sphere<double>& s = spheres_[ix];
+      const Sphere<double>& s = spheres[ix];
       kinds |= WK_SPHERE | (s.moving ? WK_MOVING : 0u);
-      put(s.c1, 0, true);
-      put(s.dc, s.r, false);
+      put(e, s.c1, 0, true);
+      put(e, s.dc, s.r, false);
     } else if (etype(e) == E_TRI) {
-      const Tri<double>& t = tris_[ix];
+      const Tri<double>& t = tris[ix];
       kinds |= WK_TRI;
-      put(t.p0, 0, true);
-      put(t.e1, 0, false);
-      put(t.e2, 0, false);
+      put(e, t.p0, 0, true);
+      put(e, t.e1, 0, false);
+      put(e, t.e2, 0, false);
     } else if (etype(e) == E_QUAD) {
-      const Quad<double>& q = quads_[ix];
+      const Quad<double>& q = quads[ix];
       kinds |= WK_QUAD;
-      put(q.q, 0, true);
-      put(q.n, q.D, false);
-      put(q.a, 0, false);
-      put(q.b, 0, false);
+      put(e, q.q, 0, true);
+      put(e, q.n, q.D, false);
+      put(e, q.a, 0, false);
+      put(e, q.b, 0, false);
     } else {
       return false;
     }
     return true;
-  };
-  for (const Item& it : big)
-    if (!put_prim(it.entry)) return false;
-  // a leaf's words are emitted once; the 8-wide tree below refers to the same words
-  std::vector<int64_t> leaf_memo(bn.size(), -1);
-  auto leaf_code = [&](int b, uint32_t& code) {
-    if (leaf_memo[(size_t)b] >= 0) {
-      code = (uint32_t)leaf_memo[(size_t)b];
-      return true;
-    }
-    const BN& nd = bn[(size_t)b];
+  }
+  bool leaf_code(int b, uint32_t& code) {  // (emit reaches every leaf once)
+    const BinNode& nd = bn[(size_t)b];
     const size_t first = words.size();
     if (nd.count == 0 || nd.count > 64 || first > kWFirstMask) return false;
     for (size_t i = nd.first; i < nd.first + nd.count; i++)
       if (!put_prim(prims[order[i]].entry)) return false;
     code = kWLeaf | (uint32_t)(nd.count - 1) << kWCountShift | (uint32_t)first;
-    leaf_memo[(size_t)b] = code;
     return true;
-  };
+  }
   // the children of binary node b in a `width`-wide node: open the child of largest area until full
-  auto collapse = [&](int b, size_t width) {
-    const BN& nd = bn[(size_t)b];
-    std::vector<int> ch{nd.left, nd.right};
+  std::vector<int> collapse(int b, size_t width) const {
+    std::vector<int> ch{bn[(size_t)b].left, bn[(size_t)b].right};
     while (ch.size() < width) {
       int pick = -1;
       double best = -1;
       for (size_t k = 0; k < ch.size(); k++) {
-        const BN& c = bn[(size_t)ch[k]];
+        const BinNode& c = bn[(size_t)ch[k]];
         if (c.left >= 0 && c.box.area() > best) {
           best = c.box.area();
           pick = (int)k;
         }
       }
       if (pick < 0) break;
-      const BN& c = bn[(size_t)ch[(size_t)pick]];
+      const BinNode& c = bn[(size_t)ch[(size_t)pick]];
       const int l = c.left, r = c.right;
       ch[(size_t)pick] = l;
       ch.insert(ch.begin() + pick + 1, r);
     }
     return ch;
-  };
-  std::vector<WNode> wn;
-  // collapse: node of binary node `b` -> its index; stack need returned through `need`
-  std::function<bool(int, uint32_t&, int&)> emit = [&](int b, uint32_t& code, int& need) -> bool {
-    const BN& nd = bn[(size_t)b];
-    if (nd.left < 0) {
+  }
+  // binary node b -> its leaf code or the index of its wide node; need: the stack entries below it
+  bool emit(int b, uint32_t& code, int& need) {
+    if (bn[(size_t)b].left < 0) {
       need = 0;
       return leaf_code(b, code);
     }
@@ -1421,101 +1396,108 @@ bool Compiler::wide_bvh(const std::vector<Item>& all, CompiledScene* out) {
     need = (int)ch.size() - 1 + sub;
     code = (uint32_t)idx;
     return true;
-  };
-  uint32_t root;
-  int need;
-  const bool ok = emit(0, root, need);
-  // The top of the tree first (round 5): the nodes of the first levels, in breadth-first order, take
-  // indices [0, top) -- kernels over a tree in HBM keep them in LDS (every ray visits them) -- and the rest
-  // keep their depth-first order (subtrees contiguous). The deepest level that fits kWideTopMax nodes.
-  uint32_t top = 0;
-  if (ok && !(root & kWLeaf) && wn.size() > 1) {
-    std::vector<uint32_t> bfs{root}, level{root};
-    std::vector<uint32_t> chosen;
-    for (int depth = 0; depth < 8 && !level.empty(); depth++) {
-      if (bfs.size() > kWideTopMax) break;
-      chosen = bfs;
-      std::vector<uint32_t> next;
-      for (uint32_t n : level)
-        for (int c = 0; c < 4; c++)
-          if (!(wn[n].child[c] & kWLeaf)) next.push_back(wn[n].child[c]);
-      bfs.insert(bfs.end(), next.begin(), next.end());
-      level.swap(next);
-    }
-    top = (uint32_t)chosen.size();
-    std::vector<uint32_t> perm(wn.size(), 0xFFFFFFFFu);
-    uint32_t k = 0;
-    for (uint32_t n : chosen) perm[n] = k++;
-    for (uint32_t n = 0; n < wn.size(); n++)
-      if (perm[n] == 0xFFFFFFFFu) perm[n] = k++;
-    std::vector<WNode> re(wn.size());
-    for (uint32_t n = 0; n < wn.size(); n++) {
-      WNode w = wn[n];
-      for (int c = 0; c < 4; c++)
-        if (!(w.child[c] & kWLeaf)) w.child[c] = perm[w.child[c]];
-      re[perm[n]] = w;
-    }
-    wn.swap(re);
-    root = perm[root];
   }
+};
+
+// The top of the tree first (round 5): the nodes of the first levels, in breadth-first order, take
+// indices [0, top) -- kernels over a tree in HBM keep them in LDS (every ray visits them) -- and the rest
+// keep their depth-first order (subtrees contiguous). The deepest level that fits kWideTopMax nodes. Returns top.
+uint32_t wide_top_first(std::vector<WNode>& wn, uint32_t& root) {
+  if ((root & kWLeaf) || wn.size() <= 1) return 0;
+  std::vector<uint32_t> bfs{root}, level{root};
+  std::vector<uint32_t> chosen;
+  for (int depth = 0; depth < 8 && !level.empty(); depth++) {
+    if (bfs.size() > kWideTopMax) break;
+    chosen = bfs;
+    std::vector<uint32_t> next;
+    for (uint32_t n : level)
+      for (int c = 0; c < 4; c++)
+        if (!(wn[n].child[c] & kWLeaf)) next.push_back(wn[n].child[c]);
+    bfs.insert(bfs.end(), next.begin(), next.end());
+    level.swap(next);
+  }
+  std::vector<uint32_t> perm(wn.size(), 0xFFFFFFFFu);
+  uint32_t k = 0;
+  for (uint32_t n : chosen) perm[n] = k++;
+  for (uint32_t n = 0; n < wn.size(); n++)
+    if (perm[n] == 0xFFFFFFFFu) perm[n] = k++;
+  std::vector<WNode> re(wn.size());
+  for (uint32_t n = 0; n < wn.size(); n++) {
+    WNode w = wn[n];
+    for (int c = 0; c < 4; c++)
+      if (!(w.child[c] & kWLeaf)) w.child[c] = perm[w.child[c]];
+    re[perm[n]] = w;
+  }
+  wn.swap(re);
+  root = perm[root];
+  return (uint32_t)chosen.size();
+}
+
+bool Compiler::wide_bvh(const std::vector<Item>& all, CompiledScene* out) {
+  // Primitives whose box covers a large part of the scene (the RTOW ground sphere, r = 1000) would
+  // sit in a leaf that almost every ray reaches, beside leaves of small primitives whose tests
+  // diverge from it. They are tested first, by every lane alike, before the tree (whose traversal
+  // then starts with their hit distance as its bound).
+  std::vector<Item> prims, big;
+  Box scene;
+  for (const Item& it : all) scene.grow(it.box);
+  const double sa = scene.area();
+  for (const Item& it : all) (sa > 0 && it.box.area() > 0.25 * sa && big.size() < 4 ? big : prims).push_back(it);
+  if (prims.size() < 2) {
+    prims = all;
+    big.clear();
+  }
+  bool all_spheres = true;
+  for (const Item& it : prims) all_spheres = all_spheres && etype(it.entry) == E_SPHERE;
+  BuildSet set(prims);
+  const std::vector<BinNode> bn = wide_binary_tree(set, all_spheres);
+
+  WideEmit t{quads_, spheres_, tris_, prims, set.order, bn};
+  for (const Item& it : big)
+    if (!t.put_prim(it.entry)) return false;
+  uint32_t root = 0;
+  int need = 0;
+  const bool ok = t.emit(0, root, need);
+  const uint32_t top = ok ? wide_top_first(t.wn, root) : 0;
   if (std::getenv("RT_DEBUG_WIDE"))
-    std::fprintf(stderr, "[wide] ok %d need %d nodes %zu words %zu binary nodes %zu\n", (int)ok, need, wn.size(),
-                 words.size(), bn.size());
+    std::fprintf(stderr, "[wide] ok %d need %d nodes %zu words %zu binary nodes %zu\n", (int)ok, need, t.wn.size(),
+                 t.words.size(), bn.size());
   if (!ok || need > kWideStackMax) return false;
   // the HBM kernels address nodes and primitive words by 32-bit byte offsets from the tree's base (fp32
   // rays: node * sizeof(WNode), word * 16; fp64 rays: node * sizeof(WNodeH), word * 32): a tree past 4 GiB
   // (~40 M nodes) takes the binary BVH instead
-  if ((uint64_t)wn.size() * std::max(sizeof(WNode), sizeof(WNodeH)) >= (1ull << 32) ||
-      ((uint64_t)words.size() + 2) * 32u >= (1ull << 32))
+  if ((uint64_t)t.wn.size() * std::max(sizeof(WNode), sizeof(WNodeH)) >= (1ull << 32) ||
+      ((uint64_t)t.words.size() + 2) * 32u >= (1ull << 32))
     return false;
 
   // two zero words past the last record: kernels with triangles read a record's next two words with
   // its first (trace_wide test_prims), past the end for a trailing sphere
-  words.push_back({0.f, 0.f, 0.f, 0.f});
-  words.push_back({0.f, 0.f, 0.f, 0.f});
-  words64.push_back({0, 0, 0, 0});
-  words64.push_back({0, 0, 0, 0});
-  const std::vector<WNodeH> wh = half_nodes(wn);
-  {  // the fp64 blob: the same float nodes, the double words
-    SceneHeader& h = out->hdr64;
-    h.off_wnodes = append(out->blob64, wn);
-    h.off_wnodesh = append(out->blob64, wh);
-    h.has_wnodesh = 1;
-    h.off_wprims = append(out->blob64, words64);
-    out->blob64.resize((out->blob64.size() + 255) & ~size_t(255));
-    h.bytes = out->blob64.size();
-    h.n_wnodes = (uint32_t)wn.size();
-    h.n_wprim_words = (uint32_t)words64.size();
+  t.words.resize(t.words.size() + 2, {0.f, 0.f, 0.f, 0.f});
+  t.words64.resize(t.words64.size() + 2, {0, 0, 0, 0});
+  const std::vector<WNodeH> wh = half_nodes(t.wn);
+  // only fp64 rays read the fp16 form (RT_WIDE_HALF_F64): it stays out of the fp32 blob
+  auto write_wide = [&](SceneHeader& h, std::vector<unsigned char>& blob, const auto& words, bool with_half) {
+    h.off_wnodes = append(blob, t.wn);
+    if (with_half) h.off_wnodesh = append(blob, wh);
+    h.has_wnodesh = with_half ? 1 : 0;
+    h.off_wprims = append(blob, words);
+    h.bytes = pad256(blob);
+    h.n_wnodes = (uint32_t)t.wn.size();
+    h.n_wprim_words = (uint32_t)words.size();
     h.wroot = root;
     h.wide_stack = (uint32_t)std::max(1, need);
-    h.wide_kinds = kinds;
+    h.wide_kinds = t.kinds;
     h.wide_big = (uint32_t)big.size();
     h.wide_top = top;
     h.has_wide = 1;
-  }
-  SceneHeader& h = out->hdr;
-  h.off_wnodes = append(out->blob32, wn);
-  h.has_wnodesh = 0;  // only fp64 rays read the fp16 form (RT_WIDE_HALF_F64): it stays out of the fp32 blob
-  h.off_wprims = append(out->blob32, words);
-  out->blob32.resize((out->blob32.size() + 255) & ~size_t(255));
-  h.bytes = out->blob32.size();
-  h.n_wnodes = (uint32_t)wn.size();
-  h.n_wprim_words = (uint32_t)words.size();
-  h.wroot = root;
-  h.wide_stack = (uint32_t)std::max(1, need);
-  h.wide_kinds = kinds;
-  h.wide_big = (uint32_t)big.size();
-  h.wide_top = top;
-  h.has_wide = 1;
+  };
+  write_wide(out->hdr64, out->blob64, t.words64, true);  // the same float nodes, the double words
+  write_wide(out->hdr, out->blob32, t.words, false);
   return true;
 }
 
-bool Compiler::run(CompiledScene* out, std::string* err) {
-  if (!d_) {
-    *err = "null scene descriptor";
-    return false;
-  }
-  // textures (texture.h:12-63) and materials (material.h:57-219)
+// Textures (texture.h:12-63) and materials (material.h:57-219) -> texs_, texdata_, images_, mats_ and mat_remap_.
+bool Compiler::compile_materials() {
   for (int i = 0; i < d_->num_textures; i++) {
     const rt_texture& t = d_->textures[i];
     Texture<double> r{};
@@ -1531,10 +1513,8 @@ bool Compiler::run(CompiledScene* out, std::string* err) {
       r.scale = t.scale;
     } else if (t.kind == RT_TEX_PERLIN) {  // texture.h:80-92: the tables perlin's constructor drew
       const int64_t need = 3 * kPerlinPoints + 3 * kPerlinPoints;  // rand_offset, perm_x, perm_y, perm_z
-      if (!d_->tex_data || t.data < 0 || (int64_t)t.data + need > d_->num_tex_data) {
-        *err = "perlin texture " + std::to_string(i) + ": tex_data too short";
-        return false;
-      }
+      if (!d_->tex_data || t.data < 0 || (int64_t)t.data + need > d_->num_tex_data)
+        return fail("perlin texture " + std::to_string(i) + ": tex_data too short");
       const double* src = d_->tex_data + t.data;
       r.kind = T_PERLIN;
       r.scale = t.scale;
@@ -1542,19 +1522,15 @@ bool Compiler::run(CompiledScene* out, std::string* err) {
       texdata_.insert(texdata_.end(), src, src + 3 * kPerlinPoints);  // rand_offset
       for (uint32_t k = 0; k < kPerlinPoints; k++) {  // perm_x: the only one noise.h:36 reads
         const double v = src[3 * kPerlinPoints + k];
-        if (!(v >= 0 && v < kPerlinPoints)) {
-          *err = "perlin texture " + std::to_string(i) + ": permutation entry out of range";
-          return false;
-        }
+        if (!(v >= 0 && v < kPerlinPoints))
+          return fail("perlin texture " + std::to_string(i) + ": permutation entry out of range");
         texdata_.push_back(v);
       }
     } else if (t.kind == RT_TEX_VALUE) {  // texture.h:95-103: n^3 values
       const double n = t.scale;
       if (!(n >= 1 && n <= 1024 && n == (double)(int64_t)n) || !d_->tex_data || t.data < 0 ||
-          (int64_t)t.data + (int64_t)(n * n * n) > d_->num_tex_data) {
-        *err = "value texture " + std::to_string(i) + ": bad resolution or tex_data too short";
-        return false;
-      }
+          (int64_t)t.data + (int64_t)(n * n * n) > d_->num_tex_data)
+        return fail("value texture " + std::to_string(i) + ": bad resolution or tex_data too short");
       r.kind = T_VALUE;
       r.n = (uint32_t)n;
       r.data = (uint32_t)texdata_.size();
@@ -1562,10 +1538,8 @@ bool Compiler::run(CompiledScene* out, std::string* err) {
     } else if (t.kind == RT_TEX_IMAGE) {  // texture.h:65-78: width x height RGB bytes
       const double w = t.color[0], hh = t.color[1];
       if (!(w >= 0 && hh >= 0 && w == (double)(int64_t)w && hh == (double)(int64_t)hh && w * hh <= 1e9) ||
-          (w * hh > 0 && (!d_->image_data || t.data < 0 || (int64_t)t.data + (int64_t)(w * hh * 3) > d_->num_image_data))) {
-        *err = "image texture " + std::to_string(i) + ": bad size or image_data too short";
-        return false;
-      }
+          (w * hh > 0 && (!d_->image_data || t.data < 0 || (int64_t)t.data + (int64_t)(w * hh * 3) > d_->num_image_data)))
+        return fail("image texture " + std::to_string(i) + ": bad size or image_data too short");
       r.kind = T_IMAGE;
       r.n = (uint32_t)w;
       r.h = (uint32_t)hh;
@@ -1576,25 +1550,29 @@ bool Compiler::run(CompiledScene* out, std::string* err) {
       r.kind = t.kind == RT_TEX_WORLEY ? T_WORLEY : T_VORONOI;
       cell_noise_ = true;
     } else {
-      *err = "texture kind " + std::to_string(t.kind) + " is not implemented on the device";
-      return false;
+      return fail("texture kind " + std::to_string(t.kind) + " is not implemented on the device");
     }
     texs_.push_back(r);
   }
   for (int i = 0; i < d_->num_materials; i++) {
     const rt_material& m = d_->materials[i];
-    if (m.texture < 0 || m.texture >= d_->num_textures) {
-      *err = "material " + std::to_string(i) + " has no valid texture";
-      return false;
-    }
-    if (m.kind < RT_MAT_LAMBERTIAN || m.kind > RT_MAT_GLOSS) {
-      *err = "material kind " + std::to_string(m.kind) + " is not implemented on the device";
-      return false;
-    }
+    if (m.texture < 0 || m.texture >= d_->num_textures)
+      return fail("material " + std::to_string(i) + " has no valid texture");
+    if (m.kind < RT_MAT_LAMBERTIAN || m.kind > RT_MAT_GLOSS)
+      return fail("material kind " + std::to_string(m.kind) + " is not implemented on the device");
     // gloss: interval(0, 1).clamp(smoothness) (material.h:149, interval.h) -- NaN passes through
     const float sm = m.smoothness < 0.f ? 0.f : (m.smoothness > 1.f ? 1.f : m.smoothness);
-    Material<double> r{m.kind, m.texture, (double)m.fuzz, (double)m.refraction, (double)sm,
-                       (double)m.specular_prob, {0, 0}, texs_[m.texture]};
+    // Material<double> has a hole between pad and the 16-aligned tx: zero the storage first, so that every byte
+    // of the uploaded blob is defined by the descriptor alone (tests/test_compile_digest.py)
+    Material<double> r;
+    std::memset(&r, 0, sizeof r);
+    r.kind = m.kind;
+    r.tex = m.texture;
+    r.fuzz = (double)m.fuzz;
+    r.refr = (double)m.refraction;
+    r.smooth = (double)sm;
+    r.spec = (double)m.specular_prob;
+    r.tx = texs_[m.texture];
     // value-identical materials share one record (main.cc:476-484 gives each of Sponza's
     // 262k triangles its own lambertian(solid_color(1))): the key is everything shading reads
     std::string key;
@@ -1614,59 +1592,35 @@ bool Compiler::run(CompiledScene* out, std::string* err) {
     auto it = mat_index_.find(key);
     if (it == mat_index_.end()) {
       it = mat_index_.emplace(key, (int32_t)mats_.size()).first;
-      mats_.push_back(r);
+      mats_.emplace_back();
+      std::memcpy(&mats_.back(), &r, sizeof r);  // the hole's zeros too (a copy constructor may skip them)
     }
     mat_remap_.push_back(it->second);
   }
-  if (d_->background >= d_->num_textures) {
-    *err = "background texture out of range";
-    return false;
-  }
-  std::vector<Item> top;
+  if (d_->background >= d_->num_textures) return fail("background texture out of range");
+  return true;
+}
+
+// The world's items in `top` (gather), the light, and the root entry over them.
+bool Compiler::build_root(std::vector<Item>& top, Item& root) {
   gather(d_->world, {}, top, false);
   if (ok_) light_from(d_->light);
-  if (!ok_) {
-    *err = err_;
-    return false;
-  }
+  if (!ok_) return false;
   // the world object itself decides ordering: a list stays a list when it holds a volume or is small
-  const rt_object* w = &d_->objects[d_->world];
-  bool ordered = (w->kind == RT_OBJ_LIST);
-  Item root;
   if (top.empty()) {
     root = list_of(top);
-  } else if (ordered) {
+  } else if (d_->objects[d_->world].kind == RT_OBJ_LIST) {
     root = container(top, false);
   } else {
-    root = top.size() == 1 ? top[0] : bvh(top, 0, top.size(), 0);
+    root = top.size() == 1 ? top[0] : bvh(top);
   }
-  if (root.need + 1 > kStackDepth) {
-    *err = "scene needs a deeper traversal stack than the device provides";
-    return false;
-  }
-  Item lin_top;
-  join_lin(lin_top, top);
-  std::vector<LinRec<double>> linear;
-  if (lin_top.lin_ok)
-    for (uint32_t op : lin_top.lin) linear.push_back(lin_record(op));
-  // the flat program of both blobs, when the linear program has that form (may add quad records)
-  std::vector<FlatQuadT<double>> fq;
-  std::vector<FlatBoxT<double>> fb;
-  std::vector<FlatRoomT<double>> fr;
-  std::vector<FlatQuadT<double>> fq_all;  // the quad groups with the rooms' faces still in them
-  uint32_t nq[3] = {0, 0, 0}, nq_all[3] = {0, 0, 0};
-  out->desc_quads = (int)quads_.size();
-  const bool has_flat =
-      lin_top.lin_ok && !lin_top.lin.empty() && flat_program(lin_top.lin, fq, nq, fb, fr, fq_all, nq_all);
-  if (has_flat) {
-    out->flat_quads = (int)fq_all.size();  // a room's walls count as the quads they are
-    out->flat_boxes = (int)fb.size();
-    out->flat_rooms = (int)fr.size();
-    for (const FlatRoomT<double>& r : fr) out->room_masks.push_back(r.present);
-  }
-  out->stack_need = std::max(1, root.need);
-  out->bvh_depth = root.depth;
-  out->num_items = (int)top.size();
+  if (root.need + 1 > kStackDepth) return fail("scene needs a deeper traversal stack than the device provides");
+  return true;
+}
+
+// Both blobs and their headers' offsets and counts: the records, the fp32 blob's copy of the fp64 quads, and
+// the flat program where there is one.
+void Compiler::pack_blobs(CompiledScene* out, const std::vector<LinRec<double>>& linear, const FlatProgram* flat) const {
   out->hdr64 =
       pack(out->blob64, quads_, spheres_, tris_, insts_, vols_, nodes_, refs_, mats_, texs_, light_, linear, texdata_, images_);
   out->hdr = pack(out->blob32, map32(quads_), map32(spheres_), map32(tris_), map32(insts_), map32(vols_),
@@ -1674,59 +1628,28 @@ bool Compiler::run(CompiledScene* out, std::string* err) {
   if (!quads_.empty()) {  // the fp32 quad test re-decides hits near an edge in fp64 (rt_device.h quad_t)
     out->hdr.off_quads64 = append(out->blob32, quads_);
     out->hdr.has_quads64 = 1;
-    out->blob32.resize((out->blob32.size() + 255) & ~size_t(255));
-    out->hdr.bytes = out->blob32.size();
+    out->hdr.bytes = pad256(out->blob32);
   }
-  if (has_flat) {
-    std::vector<FlatQuadT<float>> fq32;
-    std::vector<FlatBoxT<float>> fb32;
-    std::vector<FlatRoomT<float>> fr32;
-    for (const FlatQuadT<double>& q : kFlatRoomsF32 ? fq : fq_all)
-      fq32.push_back({(float)q.plane, (float)q.lo_u, (float)q.lo_w, (float)q.inv_u, (float)q.inv_w, q.e, q.inst, q.nm});
-    for (const FlatRoomT<double>& b : fr) {
-      if (!kFlatRoomsF32) break;
-      FlatRoomT<float> r{};
-      for (int k = 0; k < 3; k++) {
-        r.lo[k] = (float)b.lo[k];
-        r.hi[k] = (float)b.hi[k];
-      }
-      r.inst = b.inst;
-      r.present = b.present;
-      for (int f = 0; f < 6; f++) r.e[f] = b.e[f], r.nm[f] = b.nm[f];
-      fr32.push_back(r);
-    }
-    for (const FlatBoxT<double>& b : fb) {
-      FlatBoxT<float> r{};
-      for (int k = 0; k < 3; k++) {
-        r.lo[k] = (float)b.lo[k];
-        r.hi[k] = (float)b.hi[k];
-      }
-      r.inst = b.inst;
-      r.mat = b.mat;
-      for (int f = 0; f < 6; f++) r.face[f] = b.face[f];
-      r.neg = b.neg;
-      fb32.push_back(r);
-    }
-    auto put = [&](std::vector<unsigned char>& blob, SceneHeader& h, const auto& q, const uint32_t* n, const auto& b,
-                   const auto& r) {
-      h.off_flat_quad = append(blob, q);
-      // boxes and rooms as one array of bytes: the rooms start where the boxes end (rt_types.h flat_rooms)
-      std::vector<unsigned char> br(b.size() * sizeof(b[0]) + r.size() * sizeof(r[0]));
-      if (!b.empty()) memcpy(br.data(), b.data(), b.size() * sizeof(b[0]));
-      if (!r.empty()) memcpy(br.data() + b.size() * sizeof(b[0]), r.data(), r.size() * sizeof(r[0]));
-      h.off_flat_box = append(blob, br);
-      h.off_flat_room = h.off_flat_box + b.size() * sizeof(b[0]);
-      blob.resize((blob.size() + 255) & ~size_t(255));
-      h.bytes = blob.size();
-      for (int a = 0; a < 3; a++) h.n_flat_quad[a] = n[a];
-      h.n_flat_box = (uint32_t)b.size();
-      h.n_flat_room = (uint32_t)r.size();
-      h.has_flat = 1;
-    };
-    put(out->blob32, out->hdr, fq32, kFlatRoomsF32 ? nq : nq_all, fb32, fr32);
-    put(out->blob64, out->hdr64, fq, nq, fb, fr);
-  }
-  // the query tables: (object, that object's material) per record, quads | spheres | triangles | volumes
+  if (!flat) return;
+  auto put = [](std::vector<unsigned char>& blob, SceneHeader& h, const auto& q, const uint32_t* n, const auto& b,
+                const auto& r) {
+    h.off_flat_quad = append(blob, q);
+    h.off_flat_box = append_pair(blob, b, r);
+    h.off_flat_room = h.off_flat_box + b.size() * sizeof(b[0]);
+    h.bytes = pad256(blob);
+    for (int a = 0; a < 3; a++) h.n_flat_quad[a] = n[a];
+    h.n_flat_box = (uint32_t)b.size();
+    h.n_flat_room = (uint32_t)r.size();
+    h.has_flat = 1;
+  };
+  // the fp32 blob keeps a room's walls as quads unless kFlatRoomsF32 (rt_scene.h)
+  put(out->blob32, out->hdr, map32(kFlatRoomsF32 ? flat->quads : flat->quads_all), kFlatRoomsF32 ? flat->nq : flat->nq_all,
+      map32(flat->boxes), kFlatRoomsF32 ? map32(flat->rooms) : std::vector<FlatRoomT<float>>());
+  put(out->blob64, out->hdr64, flat->quads, flat->nq, flat->boxes, flat->rooms);
+}
+
+// The query tables: (object, that object's material) per record, quads | spheres | triangles | volumes.
+void Compiler::id_tables(CompiledScene* out) const {
   out->ids.clear();
   uint32_t tab = 0;
   for (const std::vector<int32_t>* v : {&quad_obj_, &sphere_obj_, &tri_obj_, &vol_obj_}) {
@@ -1736,6 +1659,40 @@ bool Compiler::run(CompiledScene* out, std::string* err) {
       out->ids.push_back(oi >= 0 ? d_->objects[oi].material : -1);
     }
   }
+}
+
+bool Compiler::run(CompiledScene* out, std::string* err) {
+  if (!d_) {
+    *err = "null scene descriptor";
+    return false;
+  }
+  std::vector<Item> top;
+  Item root;
+  if (!compile_materials() || !build_root(top, root)) {
+    *err = err_;
+    return false;
+  }
+  out->stack_need = std::max(1, root.need);
+  out->bvh_depth = root.depth;
+  out->num_items = (int)top.size();
+  // the linear program, and the flat program of both blobs when the linear program has that form (may add
+  // quad records)
+  Item lin_top;
+  join_lin(lin_top, top);
+  std::vector<LinRec<double>> linear;
+  if (lin_top.lin_ok)
+    for (uint32_t op : lin_top.lin) linear.push_back(lin_record(op));
+  out->desc_quads = (int)quads_.size();
+  FlatProgram flat;
+  const bool has_flat = lin_top.lin_ok && !lin_top.lin.empty() && flat_program(lin_top.lin, flat);
+  if (has_flat) {
+    out->flat_quads = (int)flat.quads_all.size();  // a room's walls count as the quads they are
+    out->flat_boxes = (int)flat.boxes.size();
+    out->flat_rooms = (int)flat.rooms.size();
+    for (const FlatRoomT<double>& r : flat.rooms) out->room_masks.push_back(r.present);
+  }
+  pack_blobs(out, linear, has_flat ? &flat : nullptr);
+  id_tables(out);
   // the wide BVH (fp32) when the world is a BVH over world-level primitives only
   bool prims_only = etype(root.entry) == E_NODE;
   for (const Item& it : top) prims_only = prims_only && etype(it.entry) <= E_TRI;
