@@ -266,7 +266,8 @@ __device__ __forceinline__ uint32_t grab_batch(uint32_t* heads, uint32_t n_items
 // call, in divergent code): consecutive items from the wave's queue, refilled one batch at a
 // time by the lowest calling lane. Every value below is identical in the calling lanes.
 // kNoItem: the frame is exhausted and the lane retires (queue state [kNoItem, kNoItem)).
-template <class R>
+// RUNS: the queue hands out the p.n_units units of a kernel that takes runs (begin_item RUNS), not the p.n_items items
+template <bool RUNS = false, class R>
 __device__ __forceinline__ uint32_t next_item_dyn(const Params<R>& p) {
   uint32_t* wq = wave_queue();
   const uint64_t need = __ballot(1);
@@ -285,14 +286,14 @@ __device__ __forceinline__ uint32_t next_item_dyn(const Params<R>& p) {
     off += take;
     if (off >= k || qe == kNoItem) break;  // served, or the wave already found every head dry
     uint32_t b = kNoItem;
-    if (lane == leader) b = grab_batch(p.heads, p.n_items);
+    if (lane == leader) b = grab_batch(p.heads, RUNS ? p.n_units : p.n_items);
     b = __shfl(b, (int)leader);
     if (b == kNoItem) {  // remember it: a dry scan stalls the wave for kHeads atomics
       qn = qe = kNoItem;
       break;
     }
     qn = b;
-    qe = min(b + kQBatch, p.n_items);
+    qe = min(b + kQBatch, RUNS ? p.n_units : p.n_items);
   }
   if (lane == leader) {
     __hip_atomic_store(wq, qn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
@@ -305,15 +306,19 @@ __device__ __forceinline__ uint32_t next_item_dyn(const Params<R>& p) {
 // items of p.tail_chunk (the item layout, rt_plan.h). `lchunk`: the item's chunk within this pass (item =
 // lchunk * npix + the pixel's index); the layout is decided by the frame's chunk, lchunk + chunk0.
 template <class R>
-__device__ __forceinline__ void item_range(const Params<R>& p, uint32_t item, uint32_t& lchunk, uint32_t& first,
-                                           uint32_t& end) {
-  lchunk = (uint32_t)(((uint64_t)item * p.npix_m) >> p.npix_k);
+__device__ __forceinline__ void chunk_range(const Params<R>& p, uint32_t lchunk, uint32_t& first, uint32_t& end) {
   const uint32_t chunk = lchunk + p.chunk0;
   // fp64 items are uniform (the host never gives them a tail): compiled out, the select costs
   // the fp64 Cornell kernel 10 VGPRs, 3 -> 2 waves per SIMD (C2 f64 5.22 -> 4.08 Gsamples/s)
   const bool bulk = chunk < p.k_bulk;
   first = bulk ? chunk * p.chunk : p.k_bulk * p.chunk + (chunk - p.k_bulk) * p.tail_chunk;
   end = min(first + (bulk ? p.chunk : p.tail_chunk), p.spp);
+}
+template <class R>
+__device__ __forceinline__ void item_range(const Params<R>& p, uint32_t item, uint32_t& lchunk, uint32_t& first,
+                                           uint32_t& end) {
+  lchunk = (uint32_t)(((uint64_t)item * p.npix_m) >> p.npix_k);
+  chunk_range(p, lchunk, first, end);
 }
 // the pixel's RNG key and the end of the item's samples: kept, or (LEAN) recomputed
 // RAYS (here, begin_item, begin_sample): the kernel's paths start on the rays of a batch (rt_radiance), not on a
@@ -346,13 +351,23 @@ __device__ __forceinline__ uint32_t send_of(const Params<R>& p, const PS& s) {
 // development build (scripts/dev_item_clocks.py): each item's duration in wall-clock ticks (100 MHz), by item
 __device__ uint32_t* g_item_clk;
 #endif
-template <bool RAYS = false, class R, class PS>
+// RUNS: `item` is a unit of the wave queue (rt_plan.h RunPlan): the slot takes the unit's first item, and shade
+// walks the rest of a run.
+template <bool RAYS = false, bool RUNS = false, class R, class PS>
 __device__ __forceinline__ void begin_item(const Params<R>& p, PS& s, uint32_t item) {
 #ifdef RT_ITEM_CLOCKS
   s.t0_ = wall_clock64();
 #endif
   uint32_t lchunk, first, end;
-  item_range(p, item, lchunk, first, end);
+  if constexpr (RUNS) {
+    const uint32_t q = (uint32_t)(((uint64_t)item * p.npix_m) >> p.npix_k);
+    const uint32_t runs = run_cfg_runs(p.run_cfg), lg = run_cfg_log2(p.run_cfg);
+    lchunk = unit_first_chunk(q, runs, lg);
+    item = unit_first_item(item, q * p.npix, p.npix, runs, lg);
+    chunk_range(p, lchunk, first, end);
+  } else {
+    item_range(p, item, lchunk, first, end);
+  }
   // a batch's "pixel" is the ray's index itself: no pixel map, and no per-item camera base below
   uint32_t xy = item - lchunk * p.npix;
   if constexpr (!RAYS) xy = p.pixmap[xy];
@@ -514,11 +529,12 @@ struct ShadeOf {
                         kLLI = Trav::kLLI;
   static constexpr bool kMatsLds = Trav::kTablesLds || Trav::kLL;
   static constexpr bool kRays = Trav::kRays;  // the next sample starts on a ray of the batch (begin_sample RAYS)
+  static constexpr bool kRuns = Trav::kItemRuns && !Trav::kRays;  // the queue hands out runs of items (RunPlan)
 };
 template <bool FLAT>
 struct ShadeGeneral {
   static constexpr bool kFlat = FLAT, kMoving = true, kLL = false, kNL = false, kLLI = false, kMatsLds = false;
-  static constexpr bool kRays = false;
+  static constexpr bool kRays = false, kRuns = false;
 };
 template <class R, bool CAMX, class Cfg, class PS>
 __device__ bool shade(const Params<R>& p, PS& s, R t, uint32_t e, int32_t inst, uint32_t nm = 0,
@@ -904,17 +920,30 @@ __device__ bool shade(const Params<R>& p, PS& s, R t, uint32_t e, int32_t inst, 
     dst[1] = acc.y;
     dst[2] = acc.z;
     s.set_acc(mkv(R(0), R(0), R(0)));
-    // persistent schedule: from the wave's queue; wavefront schedule: the slot's next item, P further on
-    const uint32_t nx = p.persist == kPersist ? next_item_dyn(p) : (item + p.P < p.n_items ? item + p.P : kNoItem);
-    if (nx == kNoItem) {
-      if constexpr (kInPlace) {
-        retire = true;  // (below)
-      } else {
-        s.bounce = -1;
-        return false;
-      }
+    // a chunk that is not the last of its run (rt_plan.h RunPlan): the same pixel's next bulk chunk, with the
+    // pixel, its key and the camera base as they are -- no dequeue and no begin_item
+    bool in_run = false;
+    if constexpr (Cfg::kRuns) {
+      const uint32_t runs = run_cfg_runs(p.run_cfg), lg = run_cfg_log2(p.run_cfg);
+      in_run = run_goes_on(sample, (runs << lg) * p.chunk, (p.chunk << lg) - 1);
+    }
+    if (in_run) {
+      s.set_item(item + p.npix);
+      s.set_send(sample + p.chunk);  // (a chunk inside a run is a whole bulk chunk: plan_runs)
     } else {
-      begin_item<Cfg::kRays>(p, s, nx);
+      // persistent schedule: from the wave's queue; wavefront schedule: the slot's next item, P further on
+      const uint32_t nx = p.persist == kPersist ? next_item_dyn<Cfg::kRuns>(p)
+                                                : (item + p.P < p.n_items ? item + p.P : kNoItem);  // (never with runs)
+      if (nx == kNoItem) {
+        if constexpr (kInPlace) {
+          retire = true;  // (below)
+        } else {
+          s.bounce = -1;
+          return false;
+        }
+      } else {
+        begin_item<Cfg::kRays, Cfg::kRuns>(p, s, nx);
+      }
     }
   }
   // (round 5: regenerating the finished lanes of a wave in batches -- a lane waiting idle until 16 or 32 of
@@ -957,6 +986,10 @@ struct TravDefaults {
   // where occlusion_early_exit (rt_plan.h) refuses the any-hit form. A policy without it always takes the any-hit form.
   [[maybe_unused]] static constexpr bool kClosestOccl = false;
   static constexpr bool kRays = false;  // RaysOf: the paths start on the rays of a batch, not on a camera's
+  // the persistent kernel's wave queue hands out runs of a pixel's bulk items (rt_plan.h RunPlan, kernel_takes_runs;
+  // DESIGN.md §4, round 11), not single items. Opt-in, like kCapBeforeShade: a kernel without it is the code it was
+  // (FlatTrav RUNS)
+  static constexpr bool kItemRuns = false;
 };
 // The policy `Trav` for a ray batch (rt_radiance): the same traversal, tables, path state and shade form, in a kernel of
 // its own whose begin_item / begin_sample read the batch (RAYS) -- so the camera kernels hold no trace of it.
@@ -1000,11 +1033,15 @@ struct LinearTrav : TravDefaults {
 #define RT_FLAT_WAVES_F64_LL 7  // C2 fp64: 5 waves 28.90 ms/frame, 6: 28.08 (r05c; the general kernel at 5: 31.28);
                                 // 7 (72 VGPRs + 32 B spilled, from 80): 27.94 -> 27.79 (r05w7); 8 does not fit
 #endif
-template <class R, bool TLDS = false, bool LL = false>
+// RUNS: the LL kernel's second form, whose wave queue hands out runs of items (kItemRuns). A kernel of its own, which
+// launch_step takes only for a launch that has runs: a launch without them runs the code it always ran.
+template <class R, bool TLDS = false, bool LL = false, bool RUNS = false>
 struct FlatTrav : TravDefaults {
+  static_assert(!RUNS || (TLDS && LL), "the runs form is the LL kernel's");
   static constexpr bool kFlat = true;
   static constexpr bool kTablesLds = TLDS;  // persistent kernel: Tables in LDS (fill, run_lds)
   static constexpr bool kLL = LL;           // lambertian + light scene (shade LL; the lm table)
+  static constexpr bool kItemRuns = RUNS;  // (rt_plan.h kernel_takes_runs names the same kernels)
   static constexpr int kWaves = sizeof(R) == 4 ? RT_FLAT_WAVES : (LL ? RT_FLAT_WAVES_F64_LL : RT_FLAT_WAVES_F64);
   // not lean (fp32: 72 -> 64 VGPRs, but C2 23.5 -> 24.1 ms/frame)
   static constexpr bool kNoRad = true;  // 6 VGPRs in fp64 (its item sum is in LDS)
@@ -1345,19 +1382,20 @@ __device__ __forceinline__ void persist_body(const Params<R>& p) {
     __syncthreads();
     lm = wlm_tab;
   }
+  constexpr bool kRuns = ShadeOf<Trav>::kRuns;  // item0 is then a unit of the queue (begin_item RUNS)
   uint32_t item0 = blockIdx.x * kBlock + threadIdx.x;
   if (p.persist == kPersist) {
     if ((threadIdx.x & 63) == 0) {
       __hip_atomic_store(wave_queue(), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
       __hip_atomic_store(wave_queue() + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
     }
-    item0 = next_item_dyn(p);
+    item0 = next_item_dyn<kRuns>(p);
   }
   std::conditional_t<Trav::kWide || Trav::kCapBeforeShade, uint64_t, uint32_t> segs = 0;
-  if (item0 < p.n_items) {
+  if (item0 < (kRuns ? p.n_units : p.n_items)) {
     Path<R, Trav::kColdLds, Trav::kLean, Trav::kNoRad, Trav::kThrLds> s;
     s.set_acc(mkv(R(0), R(0), R(0)));
-    begin_item<Trav::kRays>(p, s, item0);
+    begin_item<Trav::kRays, kRuns>(p, s, item0);
     begin_sample<R, CAMX, Trav::kRays>(p, s);
     if constexpr (Trav::kWide) {
       // resumable traversal: a ray paused with the wave's laggards carries on after the others shade
@@ -2048,8 +2086,8 @@ template <class R, bool SPH, bool TRI, bool VOL, bool LLI>
 struct TravName<LinearTrav<R, SPH, TRI, VOL, LLI>> {
   static std::string get() { return trav_tag<R>("LinearTrav", SPH, TRI, VOL, LLI); }
 };
-template <class R, bool TLDS, bool LL>
-struct TravName<FlatTrav<R, TLDS, LL>> {
+template <class R, bool TLDS, bool LL, bool RUNS>  // (the runs form is the LL kernel by name: rt_plan.h path_kernel_tag)
+struct TravName<FlatTrav<R, TLDS, LL, RUNS>> {
   static std::string get() { return trav_tag<R>("FlatTrav", TLDS, LL); }
 };
 template <class R, int STACK, bool LDSN>
@@ -2072,10 +2110,13 @@ const char* kernel_tag(bool persist) {  // built once per kernel: a wavefront re
 }
 // tag of the last path kernel launched on this host thread
 thread_local const char* t_kernel = "";
+// run length of its queue's units (rt_dev_last_run): 1 for a kernel whose units are items
+thread_local uint32_t t_run = 0;
 
 template <class Trav, bool CAMX, class KernelT, class R>
 void launch_one(KernelT kern, Params<R> p, uint32_t grid, hipStream_t st, size_t lds = 0) {
   t_kernel = kernel_tag<Trav, CAMX>(p.persist != 0);
+  t_run = ShadeOf<Trav>::kRuns ? 1u << run_cfg_log2(p.run_cfg) : 1u;  // (from the instantiated type, as the tag)
   if (p.persist) {  // as many blocks as the chip holds resident; lanes pull items
     int dev = 0;
     const uint32_t res = hipGetDevice(&dev) == hipSuccess ? resident_blocks((const void*)kern, dev, lds) : 0;
@@ -2231,7 +2272,9 @@ void launch_step(const LaunchParams<R>& lp, const PathKernel& k, uint32_t grid, 
   switch (k.fam) {
     case KF_FLAT:
       if constexpr (family_built(KF_FLAT)) {
-        if (k.shade == SH_LL)
+        if (k.shade == SH_LL && p.run_cfg != 0 && kernel_takes_runs(k))  // (the host plans runs for these alone)
+          launch_k<R, FlatTrav<R, true, true, true>>(p, k, grid, st);
+        else if (k.shade == SH_LL)
           launch_k<R, FlatTrav<R, true, true>>(p, k, grid, st);
         else if (k.lds)
           launch_k<R, FlatTrav<R, true>>(p, k, grid, st);
@@ -2293,6 +2336,7 @@ void launch_step(const LaunchParams<R>& lp, const PathKernel& k, uint32_t grid, 
 
 uint64_t last_grid_lanes() { return t_grid_lanes; }
 const char* last_kernel() { return t_kernel; }
+uint32_t last_run() { return t_run; }
 
 // The three query launches: with_query_family's traversal of `fam`, each in its own kernel.
 template <class R>
@@ -2429,5 +2473,8 @@ void rt_dev_last_kernel(char* buf, size_t n) {
   if (!buf || n == 0) return;
   std::snprintf(buf, n, "%s", rtd::last_kernel());
 }
+// The run length of the units that kernel's queue handed out (rt_plan.h RunPlan): L where launch_step took the runs
+// form of a kernel, 1 where the units were items, 0 before the first launch. For tests and scripts, not in rt_hip.h.
+uint32_t rt_dev_last_run(void) { return rtd::last_run(); }
 
 }  // extern "C"

@@ -51,6 +51,10 @@ struct LaunchParams {
   // the render's chunks come in passes (the partial sums of one pass fit a memory budget): this
   // launch's items are chunks [chunk0, chunk0 + n_items / npix) of every pixel
   uint32_t chunk0;
+  // what the wave queue hands out (rt_plan.h RunPlan; read by the kernels that take runs alone, FlatTrav::kItemRuns):
+  // the pass's units, n_items where the run length is 1. (This word and run_cfg below sit where the struct had
+  // padding, so every other field keeps its place and the kernarg segment its size.)
+  uint32_t n_units;
   uint64_t npix_m;  // item / npix = (item * npix_m) >> npix_k for every item < 2^31 (div_magic)
   uint32_t npix_k;
   int32_t max_depth;
@@ -74,6 +78,7 @@ struct LaunchParams {
   // camera kernels read neither, and every field they read keeps its place in the kernarg segment.
   const double* rays;
   uint32_t ray_base;
+  uint32_t run_cfg;  // rt_plan.h run_cfg_pack of the pass's RunPlan; 0: every unit is an item
 };
 constexpr int32_t kPersist = 2;
 
@@ -102,6 +107,7 @@ constexpr bool family_built(KernelFamily f) {
 template <class R>
 void launch_step(const LaunchParams<R>& p, const PathKernel& k, uint32_t grid, hipStream_t st);
 uint64_t last_grid_lanes();  // lanes of the last persistent launch_step on this host thread
+uint32_t last_run();         // run length of the units that launch's queue handed out (1: items; 0 before the first)
 const char* last_kernel();   // tag of the kernel the last launch_step on this host thread launched ("" before the first)
 
 // wavefront schedule: the first camera ray of every slot (in k's form, base or extended); live-slot count and compaction

@@ -323,6 +323,102 @@ inline ItemPlan plan_items(uint32_t spp, int32_t samples_per_item, bool flat, ui
   return pl;
 }
 
+// ------------------------------------------------------------------ item runs (what the wave queue hands out)
+// The item layout above fixes the image's rounding. What a persistent launch's queue hands out is a *unit*: a run
+// of L = 1 << run_log2 consecutive bulk chunks of one pixel, or a single item. A lane that ends a chunk inside its
+// run goes on with the same pixel's next chunk (item + npix) and skips the dequeue, the pixel map load, the pixel
+// key and the camera base; every item still writes its own partial sum, so the image does not depend on L.
+// Of a pass's local chunks [0, pc) the first runs * L -- whole runs of bulk chunks -- are run units, handed out
+// first and run-major (unit = run * npix + pixel, as today's items are chunk-major); the bulk chunks that do not
+// fill a run and the tail items follow as single units, so the launch ends on items as short as before.
+// L = 1 (runs = 0): a unit is an item. (constexpr: the kernels call these too)
+struct RunPlan {
+  uint32_t run_log2;     // L = 1 << run_log2
+  uint32_t runs;         // run units of a pixel
+  uint32_t n_units;      // units of the pass: its items less (L - 1) for every run
+  uint32_t run_samples;  // samples of a pixel's runs, runs * L * chunk
+  uint32_t run_mask;     // L * chunk - 1 (bulk chunk sizes are powers of two where runs > 0)
+};
+// The pass over chunks [chunk0, chunk0 + pc) of every one of npix pixels, in runs of `run` (a power of two).
+// Runs need a pass that begins at the pixel's first sample (chunk0 = 0: the test at a chunk end is then one on the
+// sample index as it stands), a power-of-two bulk chunk, items * L below 2^32 (unit_first_item) and at most
+// kRunCfgRunsMax runs a pixel (what run_cfg_pack holds: a caller-given item size puts no limit on a pixel's chunks,
+// where the automatic layout stops at kMaxItemsPerPixel); a pass without them has L = 1.
+constexpr uint32_t kRunCfgRunsMax = 0xFFFFu;
+inline RunPlan plan_runs(const ItemPlan& pl, uint32_t spp, uint32_t chunk0, uint32_t pc, uint32_t npix, uint32_t run) {
+  RunPlan r{};
+  // the bulk chunks that hold `chunk` samples (a caller-given item size may leave the last one short: it stays
+  // single, so a chunk inside a run always ends on a multiple of chunk)
+  const uint32_t bulk = chunk0 == 0 ? std::min({pl.k_bulk, spp / pl.chunk, pc}) : 0;
+  const bool pow2 = (pl.chunk & (pl.chunk - 1)) == 0;  // (a caller-given samples_per_item may be anything)
+  while (r.run_log2 < 16 && (2u << r.run_log2) <= run) r.run_log2++;
+  // no run longer than the bulk chunks; a shorter run has more runs a pixel, so over kRunCfgRunsMax ends at L = 1
+  while (r.run_log2 && (!pow2 || (bulk >> r.run_log2) == 0 || (bulk >> r.run_log2) > kRunCfgRunsMax ||
+                        (((uint64_t)npix * pc) << r.run_log2) >> 32))
+    r.run_log2--;
+  r.runs = r.run_log2 ? bulk >> r.run_log2 : 0;
+  r.n_units = npix * (pc - r.runs * ((1u << r.run_log2) - 1));
+  r.run_samples = (r.runs << r.run_log2) * pl.chunk;
+  r.run_mask = (pl.chunk << r.run_log2) - 1;
+  return r;
+}
+// The kernels' word for a pass's runs (LaunchParams::run_cfg): runs in the low 16 bits, run_log2 above; 0: every
+// unit is an item. plan_runs keeps runs within kRunCfgRunsMax.
+constexpr uint32_t run_cfg_pack(uint32_t runs, uint32_t run_log2) { return runs | run_log2 << 16; }
+constexpr uint32_t run_cfg_runs(uint32_t cfg) { return cfg & kRunCfgRunsMax; }
+constexpr uint32_t run_cfg_log2(uint32_t cfg) { return cfg >> 16; }
+// Unit -> the local chunk of its first item, and that item. q = unit / npix (the kernel divides by div_magic) and
+// qn = q * npix. Run unit q of a pixel starts at chunk q * L; the singles follow the runs * L chunks of the runs,
+// runs * (L - 1) chunks further on than their unit. Both as a minimum, which is cheaper on the device than a
+// select: q (L - 1) < runs (L - 1) exactly where q < runs. (qn << run_log2 stays below 2^32: plan_runs)
+constexpr uint32_t unit_first_chunk(uint32_t q, uint32_t runs, uint32_t run_log2) {
+  const uint32_t a = q << run_log2, b = q + runs * ((1u << run_log2) - 1);
+  return a < b ? a : b;
+}
+constexpr uint32_t unit_first_item(uint32_t unit, uint32_t qn, uint32_t npix, uint32_t runs, uint32_t run_log2) {
+  const uint32_t a = (qn << run_log2) - qn, b = runs * ((1u << run_log2) - 1) * npix;
+  return unit + (a < b ? a : b);
+}
+// At a chunk end: does the lane's run go on? sample: the pixel's sample index that follows the chunk (without
+// first_sample, as item_range counts). Inside the runs' samples, and not at a run's boundary.
+constexpr bool run_goes_on(uint32_t sample, uint32_t run_samples, uint32_t run_mask) {
+  return sample < run_samples && (sample & run_mask) != 0;
+}
+
+// The kernels that hand out runs (FlatTrav::kItemRuns): the flat program's LL kernels on a camera's rays. Every
+// other kernel's units are items whatever the plan says, so the host plans L = 1 for them.
+inline bool kernel_takes_runs(const PathKernel& k) {
+  return k.fam == KF_FLAT && k.shade == SH_LL && k.lds && k.persist && !k.rays;
+}
+// The automatic run length. L is pure scheduling, so it may depend on how much work the call has, and it must: a
+// run is one unit of L * chunk samples that no other lane can take over, and the launch ends when its last lane
+// does. Two conditions (has the measurements):
+//  - `overlapped`: the launch goes through the launch lanes and so did the context's launch before it (lane_plan:
+//    a stream of device-output frames), so the next launch's blocks fill the SIMDs this launch's last runs leave
+//    idle. Runs lengthen a launch's end -- C2 fp64 with one launch at a time (RT_FRAME_OVERLAP=0): 23.27 ms a frame
+//    with items, 23.50 at L = 2, 23.9 at 4, 25.2 at 8 -- and shorten everything before it; only a launch whose end
+//    is hidden gains (back to back: 22.98 -> 22.41 at L = 8). A lone frame, a host-output render and the first frame
+//    of a stream keep items; the last frame of a stream pays the longer end once.
+//  - every lane still receives many units, so that the dynamic queue still evens out the paths' lengths:
+//    kMinUnitsPerMaxLane on average over `lanes`, which the caller gives as the most lanes the device can hold (2,048
+//    a CU), not the kernel's resident grid (the headline kernel's is 1,792 a CU: 8 here is 9.1 per resident lane).
+//    The largest L up to kMaxRun that keeps it. C2 fp64, units per such lane (23 a pixel at L = 4 and 8, 30 at 2):
+//    the whole frame, 28, is fastest at L = 8 (16 is slower again: one run and 12 single bulk chunks a pixel); half
+//    of it, 14, gains at L = 4; a quarter gains nothing at 7 (L = 4) and 0.2 % at 9 (L = 2); an eighth loses 0.5 %
+//    at 4.6 (L = 2) and 3 % at 3.5 (L = 4). A C1-sized frame has 3 to 6 at any L > 1 and keeps items.
+// L = 1 for the wavefront schedule, for a kernel that does not take runs, for a ray batch (kernel_takes_runs) and
+// for a multi-pass call (plan_runs gives runs to the first pass alone, and every pass would end on long units).
+constexpr uint32_t kMaxRun = 8, kMinUnitsPerMaxLane = 8;
+inline uint32_t auto_run(const ItemPlan& pl, const PathKernel& k, uint32_t spp, uint32_t npix, uint64_t lanes,
+                         bool overlapped) {
+  if (!kernel_takes_runs(k) || pl.passes != 1 || !overlapped) return 1;
+  for (uint32_t run = kMaxRun; run > 1; run /= 2) {
+    const RunPlan r = plan_runs(pl, spp, 0, pl.nchunks, npix, run);
+    if ((1u << r.run_log2) == run && (uint64_t)r.n_units >= kMinUnitsPerMaxLane * lanes) return run;
+  }
+  return 1;
+}
+
 // ------------------------------------------------------------------ the launch lanes (frame overlap)
 // A persistent launch ends with a tail: its last paths, up to max_depth dependent segments each, run on a chip
 // that is nearly empty (a frame costs its work plus ~0.5 ms whatever its size). The next launch

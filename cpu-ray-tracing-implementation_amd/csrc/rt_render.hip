@@ -77,6 +77,7 @@ struct rt_context {
   bool inputs_written = false;   // LaneQuery::inputs_written
   bool prev_overlapped = false;  // LaneQuery::prev_overlapped
   bool lane_stale[2] = {false, false};  // LaneQuery::lane_stale
+  uint64_t max_lanes = 0;        // the most lanes the device can hold, 2,048 a CU (auto_run's bound); 0: not asked yet
   std::vector<uint8_t> ev_lane;  // per pair of timing events: recorded on a lane (settle() clamps its start)
 };
 
@@ -312,6 +313,14 @@ PlanKnobs env_knobs() {
 bool env_frame_overlap() {
   const char* v = std::getenv("RT_FRAME_OVERLAP");
   return !(v && *v) || std::strtol(v, nullptr, 10) != 0;
+}
+
+// RT_ITEM_RUN=L: the run length of the kernels that take runs (rt_plan.h RunPlan), a power of two, for A/B runs and
+// tests; 1: every unit is an item. 0 or unset: auto_run's choice. Read per call, as the knobs above.
+uint32_t env_item_run() {
+  const char* v = std::getenv("RT_ITEM_RUN");
+  const long r = (v && *v) ? std::strtol(v, nullptr, 10) : 0;
+  return r > 0 ? (uint32_t)std::min<long>(r, (long)kMaxItemsPerPixel) : 0;
 }
 
 // One launch_step, between two events when the context collects kernel times (settle() sums the pairs)
@@ -637,6 +646,14 @@ rt_status render(rt_context* c, const rt_camera_desc* cam, const rt_render_param
     lq.shared_scratch = p.sc.wide_spill != nullptr;
     lq.second_set = true;  // asked first whether the call would overlap at all; then whether the set can be had
     lq.second_set = lane_plan(lq).overlap && lanes_ready(c, plan.partial_bytes);
+    // the run length of the queue's units (rt_plan.h RunPlan) is the knob's for a kernel that takes runs, else
+    // auto_run's (below, per launch), against the most lanes the device can hold (32 waves of 64 per CU)
+    const uint32_t forced_run = kernel_takes_runs(kind) ? env_item_run() : 1;
+    if (kernel_takes_runs(kind) && c->max_lanes == 0) {
+      int ncu = 0;
+      RT_HIP(c, hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->device));
+      c->max_lanes = (uint64_t)std::max(ncu, 1) * 2048u;
+    }
     for (uint32_t c0 = 0; c0 < plan.nchunks; c0 += plan.cpp) {  // the passes (one for every BASELINE config but C5)
       const uint32_t pc = std::min(plan.cpp, plan.nchunks - c0);
       p.chunk0 = c0;
@@ -647,6 +664,12 @@ rt_status render(rt_context* c, const rt_camera_desc* cam, const rt_render_param
       lq.lane_stale[0] = c->lane_stale[0];
       lq.lane_stale[1] = c->lane_stale[1];
       const LanePlan lp = lane_plan(lq);
+      // runs only in a stream of overlapped launches, where the next launch hides this one's longer end (auto_run)
+      const uint32_t run =
+          forced_run ? forced_run : auto_run(plan, kind, spp, npix, c->max_lanes, lp.overlap && lq.prev_overlapped);
+      const RunPlan rp = plan_runs(plan, spp, c0, pc, npix, run);
+      p.n_units = rp.n_units;
+      p.run_cfg = run_cfg_pack(rp.runs, rp.run_log2);
       const R* partial = (const R*)c->partial.ptr;
       if (lp.overlap) {
         hipStream_t lane = lp.lane ? c->lane1 : c->stream;

@@ -194,6 +194,11 @@ def load():
         # a development entry point beside the C ABI (not in include/rt_hip.h): Context.last_kernel
         lib.rt_dev_last_kernel.restype = None
         lib.rt_dev_last_kernel.argtypes = [ctypes.c_char_p, ctypes.c_size_t]
+        # ... and the run length of the units its queue handed out: Context.last_run
+        # (a development build of older sources, RT_HIP_LIB, may not have it: its last_run raises AttributeError)
+        if hasattr(lib, "rt_dev_last_run"):
+            lib.rt_dev_last_run.restype = ctypes.c_uint32
+            lib.rt_dev_last_run.argtypes = []
         # ... and the kernel a render would launch, from the descriptor alone (no GPU): rt_amd.plan_kernel
         lib.rt_dev_plan_kernel.restype = None
         lib.rt_dev_plan_kernel.argtypes = [ctypes.POINTER(rt_scene_desc), c_int32, c_int32, c_int32, c_int32,

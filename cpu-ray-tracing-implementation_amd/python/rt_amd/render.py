@@ -79,6 +79,11 @@ class Context:
         self.lib.rt_dev_last_kernel(buf, len(buf))
         return buf.value.decode()
 
+    def last_run(self):
+        """The run length of the units that kernel's queue handed out (rt_dev_last_run): L where the launch took the
+        runs form of a kernel (csrc/rt_plan.h RunPlan), 1 where its units were items, 0 before the first render."""
+        return int(self.lib.rt_dev_last_run())
+
     def trace_family(self, precision=abi.RT_PREC_F64, traversal=0):
         """The traversal trace_rays takes for the uploaded scene: "FLAT", "LINEAR", "WIDE_LDS", "WIDE_HBM", "STACK"."""
         f = self.lib.rt_trace_family(self.h, precision, traversal)
