@@ -2023,6 +2023,94 @@ __global__ __launch_bounds__(kBlock) void k_resolve(const R* partial, uint32_t n
   out[3ull * px + 2] = s2;
 }
 
+// ------------------------------------------------------------------ adaptive sampling (rt_render_adaptive)
+// The resolve of a pass over a pixel list (rt_launch.h): one thread per entry j adds the pass's batch sums, in chunk
+// order and in double, to the first and second moments of the entry's pixel. The record (rt_plan.h AdaptiveAcc, one
+// 64-byte line, read and written as four 16-byte words) runs on across passes and rounds, so neither the pass split
+// nor the round a batch came in changes it; a pixel is one entry of one list at a time, so no atomics. Each product
+// and sum is rounded on its own (no contraction), as the estimator's definition counts them.
+template <class R>
+__global__ __launch_bounds__(kBlock) void k_resolve_moments(const R* partial, const uint32_t* slots, uint32_t n,
+                                                            uint32_t nchunks, AdaptiveAcc* acc) {
+#pragma clang fp contract(off)
+  const uint32_t j = blockIdx.x * kBlock + threadIdx.x;
+  if (j >= n) return;
+  AdaptiveAcc* rec = acc + (slots ? slots[j] : j);
+  AdaptiveAcc a = *rec;
+  if (partial) {  // (null: a black frame's sums, which change neither S nor Q)
+    for (uint32_t c = 0; c < nchunks; c++) {
+      const R* q = partial + 3ull * ((uint64_t)c * n + j);
+      for (int k = 0; k < 3; k++) {
+        const double s = (double)q[k];
+        a.S[k] += s;
+        a.Q[k] += s * s;
+      }
+    }
+  }
+  a.K += nchunks;
+  *rec = a;
+}
+
+// The select of a round, first step: one thread per entry computes the pixel's estimate from its record
+// (adaptive_error, the host's own copy), decides whether it stops and leaves both in the record; a pixel that stops
+// gets its three outputs (every pixel stops once, N >= max_spp at the latest). The block's survivors are counted by
+// wave ballot and popcount, per-wave counts in LDS, as k_count counts live slots; k_scan turns the counts into offsets.
+template <class R>
+__global__ __launch_bounds__(kBlock) void k_adaptive_select(SelectParams p) {
+  __shared__ uint32_t wc[kBlock / 64];
+  const uint32_t j = blockIdx.x * kBlock + threadIdx.x;
+  bool survives = false;
+  if (j < p.n) {
+    const uint32_t slot = p.slots ? p.slots[j] : j;
+    AdaptiveAcc a = p.acc[slot];
+    double mean[3], err;
+    adaptive_error(a.K, p.batch, a.S, a.Q, p.floor, mean, &err);
+    const uint32_t samples = a.K * p.batch;
+    const bool stop = adaptive_stops(err, p.threshold, samples, p.max_spp);
+    a.err = err;
+    a.stop = stop ? 1u : 0u;
+    p.acc[slot] = a;
+    if (stop) {
+      R* rgb = (R*)p.out_rgb + 3ull * slot;
+      rgb[0] = (R)mean[0];
+      rgb[1] = (R)mean[1];
+      rgb[2] = (R)mean[2];
+      p.out_spp[slot] = (int32_t)samples;
+      p.out_err[slot] = err;
+    }
+    survives = !stop;
+  }
+  const unsigned long long m = __ballot(survives);
+  if ((threadIdx.x & 63) == 0) wc[threadIdx.x >> 6] = (uint32_t)__popcll(m);
+  __syncthreads();
+  if (threadIdx.x == 0) p.blk[blockIdx.x] = wc[0] + wc[1] + wc[2] + wc[3];
+}
+// ... second step: the survivors go to the next round's list at their block's offset plus their rank in the block, so
+// the list keeps its order (as k_compact keeps the live slots'), whatever order the blocks run in.
+__global__ __launch_bounds__(kBlock) void k_adaptive_compact(SelectParams p) {
+  __shared__ uint32_t wc[kBlock / 64];
+  const uint32_t j = blockIdx.x * kBlock + threadIdx.x;
+  uint32_t slot = 0, xy = 0;
+  bool survives = false;
+  if (j < p.n) {
+    slot = p.slots ? p.slots[j] : j;
+    xy = p.pixmap[j];
+    survives = p.acc[slot].stop == 0;
+  }
+  const unsigned long long m = __ballot(survives);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) wc[wave] = (uint32_t)__popcll(m);
+  __syncthreads();
+  uint32_t base = p.blk[blockIdx.x];
+  for (int w = 0; w < wave; w++) base += wc[w];
+  if (survives) {
+    const unsigned long long below = lane ? (m & ((1ull << lane) - 1ull)) : 0ull;
+    const uint32_t at = base + (uint32_t)__popcll(below);
+    p.next_pixmap[at] = xy;
+    p.next_slots[at] = slot;
+  }
+}
+
 template <class R>
 __global__ void k_zero(R* out, uint64_t n) {
   uint64_t i = blockIdx.x * (uint64_t)kBlock + threadIdx.x;
@@ -2403,6 +2491,20 @@ void launch_resolve(const R* partial, uint32_t npix, uint32_t nchunks, uint32_t 
                      out, (int)first, (int)last);
 }
 template <class R>
+void launch_resolve_moments(const R* partial, const uint32_t* slots, uint32_t n, uint32_t nchunks, AdaptiveAcc* acc,
+                            hipStream_t st) {
+  hipLaunchKernelGGL(k_resolve_moments<R>, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, partial, slots, n,
+                     nchunks, acc);
+}
+template <class R>
+void launch_adaptive_select(const SelectParams& p, hipStream_t st) {
+  const uint32_t nb = (p.n + kBlock - 1) / kBlock;
+  hipLaunchKernelGGL(k_adaptive_select<R>, dim3(nb), dim3(kBlock), 0, st, p);
+  if (!p.next_pixmap) return;  // the last round: every pixel has stopped
+  hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, st, p.blk, nb, p.blk + nb + 1);
+  hipLaunchKernelGGL(k_adaptive_compact, dim3(nb), dim3(kBlock), 0, st, p);
+}
+template <class R>
 void launch_zero(R* out, uint64_t n, hipStream_t st) {
   hipLaunchKernelGGL(k_zero<R>, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, out, n);
 }
@@ -2417,7 +2519,9 @@ void launch_pixmap(const uint4* tiles, uint32_t ntiles, uint32_t npix, uint32_t*
   template void launch_trace<R>(const TraceParams<R>&, TraceFamily, hipStream_t);                                \
   template void launch_aov<R>(const AovParams<R>&, TraceFamily, hipStream_t);                                    \
   template void launch_occluded<R>(const OcclParams<R>&, TraceFamily, bool, hipStream_t);                        \
-  template void launch_resolve<R>(const R*, uint32_t, uint32_t, uint32_t, R*, bool, bool, hipStream_t);
+  template void launch_resolve<R>(const R*, uint32_t, uint32_t, uint32_t, R*, bool, bool, hipStream_t);          \
+  template void launch_resolve_moments<R>(const R*, const uint32_t*, uint32_t, uint32_t, AdaptiveAcc*, hipStream_t); \
+  template void launch_adaptive_select<R>(const SelectParams&, hipStream_t);
 RT_INSTANTIATE(double)
 RT_INSTANTIATE(float)
 #undef RT_INSTANTIATE

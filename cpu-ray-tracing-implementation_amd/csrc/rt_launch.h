@@ -125,6 +125,34 @@ template <class R>
 void launch_zero(R* out, uint64_t n, hipStream_t st);
 void launch_pixmap(const uint4* tiles, uint32_t ntiles, uint32_t npix, uint32_t* pixmap, hipStream_t st);
 
+// ---- adaptive sampling (rt_render_adaptive): a round's pixels are a list, entry j = (pixmap[j], the pixel's position
+// slots[j] in the call's packed outputs and accumulator records; slots null: j itself, the first round's full list).
+// The resolve of a pass over a pixel list: adds the pass's nchunks batch sums of entry j, partial[3 * (c * n + j)] in
+// chunk order, to the record acc[slot of j] (k_resolve_moments). partial null: the sums are zero (max_depth = 0).
+template <class R>
+void launch_resolve_moments(const R* partial, const uint32_t* slots, uint32_t n, uint32_t nchunks, AdaptiveAcc* acc,
+                            hipStream_t st);
+// What the select of a round needs: the round's list, the next round's, the outputs and the stopping rule.
+struct SelectParams {
+  AdaptiveAcc* acc;
+  const uint32_t* pixmap;  // the round's list, n entries
+  const uint32_t* slots;   // (null: the identity)
+  uint32_t n;
+  uint32_t* next_pixmap;   // the survivors, in the list's order (null: the last round, nobody survives)
+  uint32_t* next_slots;
+  uint32_t* blk;           // ceil(n / kBlock) + 2 words: the blocks' survivor counts, then offsets; the total last
+  void* out_rgb;           // 3 R a pixel
+  int32_t* out_spp;
+  double* out_err;
+  uint32_t batch, max_spp;
+  double threshold, floor;
+};
+// k_adaptive_select in its two steps with k_scan between them: every entry's estimate, decision and -- for a pixel
+// that stops -- outputs, and the blocks' survivor counts; then the survivors compacted in order into the next list.
+// The survivor count ends up in p.blk[ceil(n / kBlock) + 1].
+template <class R>
+void launch_adaptive_select(const SelectParams& p, hipStream_t st);
+
 // ---- ray queries (rt_trace_rays): the argument of k_trace. Its own struct: LaunchParams and DevScene are the render
 // kernels' kernarg, whose SGPR budget is tuned (reload_params), so what only a query needs lives here.
 //   rays  [n][8] doubles  o, d, time, tmax           (64 B a ray, read as four 16-byte loads)

@@ -419,6 +419,60 @@ inline uint32_t auto_run(const ItemPlan& pl, const PathKernel& k, uint32_t spp, 
   return 1;
 }
 
+// ------------------------------------------------------------------ adaptive sampling (rt_render_adaptive)
+// A pixel's running moments over its batches (rt_hip.h, "adaptive sampling"): per channel the sum S of the batch sums
+// and the sum Q of their squares, in double and in batch order, and the batch count K. One 64-byte record a pixel of
+// the call, indexed by the pixel's packed position; k_resolve_moments adds a pass's batches to it, k_adaptive_select
+// reads it and leaves the estimate and its decision in it.
+struct alignas(64) AdaptiveAcc {
+  double S[3], Q[3];
+  double err;     // the estimate the last select computed
+  uint32_t K;
+  uint32_t stop;  // that select's decision: 1 the pixel has stopped, 0 it takes the next round
+};
+static_assert(sizeof(AdaptiveAcc) == 64, "one record is one 64-byte line");
+
+// The estimator's arithmetic, the one copy the kernel and the host (rt_dev_adaptive_error) run: K >= 2 batches of
+// `batch` samples with the moments S, Q -> the channel means (in double) and err. Every operation is rounded on its
+// own (no contraction), in the order written, so a numpy transcription gives the same bits. max(0, d) is written as a
+// select that keeps a NaN: a pixel with a NaN sample has a NaN err, fails err <= threshold and runs to max_spp.
+__host__ __device__ inline void adaptive_error(uint32_t K, uint32_t batch, const double S[3], const double Q[3],
+                                               double floor, double mean3[3], double* err) {
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+  const double k = (double)K, b = (double)batch;
+  const double n = k * b;
+  double var[3];
+  for (int c = 0; c < 3; c++) {
+    mean3[c] = S[c] / n;
+    const double sq = S[c] * S[c];
+    const double d = Q[c] - sq / k;
+    var[c] = (d < 0.0 ? 0.0 : d) / (k - 1.0);
+  }
+  const double se2 = ((var[0] + var[1]) + var[2]) / (k * (b * b));
+  const double level = ((mean3[0] + mean3[1]) + mean3[2]) / 3.0;
+  *err = __builtin_sqrt(se2 / 3.0) / (floor + level);
+}
+// after a round: does the pixel stop? (a NaN err fails the comparison)
+__host__ __device__ inline bool adaptive_stops(double err, double threshold, uint32_t samples, uint32_t max_spp) {
+  return err <= threshold || samples >= max_spp;
+}
+// The parameter rules of rt_adaptive_params (rt_adaptive_check): nullptr, or what is wrong with them.
+inline const char* adaptive_params_error(const rt_adaptive_params& p) {
+  if (p.batch < 1) return "batch must be positive";
+  if (p.step_spp < p.batch || p.step_spp % p.batch != 0) return "step_spp must be a positive multiple of batch";
+  if (p.min_spp % p.step_spp != 0 || p.max_spp % p.step_spp != 0) return "min_spp and max_spp must be multiples of step_spp";
+  if ((int64_t)p.min_spp < 2 * (int64_t)p.batch) return "min_spp must hold at least two batches";
+  if (p.min_spp > p.max_spp) return "min_spp above max_spp";
+  if (p.max_depth < 0) return "max_depth must not be negative";
+  if (p.precision != RT_PREC_F32 && p.precision != RT_PREC_F64) return "unknown precision";
+  if (p.traversal != RT_TRAV_AUTO && p.traversal != RT_TRAV_ORDERED) return "unknown traversal";
+  if (!(p.threshold >= 0.0)) return "threshold must be >= 0 and not NaN";
+  if (!(p.floor > 0.0) || p.floor - p.floor != 0.0) return "floor must be positive and finite";
+  return nullptr;
+}
+
 // ------------------------------------------------------------------ the launch lanes (frame overlap)
 // A persistent launch ends with a tail: its last paths, up to max_depth dependent segments each, run on a chip
 // that is nearly empty (a frame costs its work plus ~0.5 ms whatever its size). The next launch

@@ -1,5 +1,6 @@
 // rt_render.hip -- the host side of librt_hip.so: contexts and their device buffers, render<R>() and its two
-// schedules (over a camera's tiles, or over a ray batch: rt_radiance), the query path (trace_rays<R>(), occluded<R>(),
+// schedules (over a camera's tiles, or over a ray batch: rt_radiance, or over a pixel list: a round of
+// render_adaptive<R>(), the round loop of rt_render_adaptive), the query path (trace_rays<R>(), occluded<R>(),
 // camera_rays(), render_aov<R>()), and the C ABI of include/rt_hip.h with its argument checks. It contains no kernel: what a render launches goes through
 // rt_launch.h (rt_kernels.hip), and its item layout and kernel family come from rt_plan.h.
 #include <hip/hip_runtime.h>
@@ -79,6 +80,10 @@ struct rt_context {
   bool lane_stale[2] = {false, false};  // LaneQuery::lane_stale
   uint64_t max_lanes = 0;        // the most lanes the device can hold, 2,048 a CU (auto_run's bound); 0: not asked yet
   std::vector<uint8_t> ev_lane;  // per pair of timing events: recorded on a lane (settle() clamps its start)
+  // adaptive sampling (rt_render_adaptive): the pixels' moment records, the two pixel lists the rounds alternate
+  // between (positions, and the pixels' slots in the outputs and records), the select's block counts, and device
+  // copies of a host-pointer call's out_spp and out_err (out_rgb's is out_tmp)
+  DevBuf ad_acc, ad_pix[2], ad_slot[2], ad_blk, ad_spp, ad_err;
 };
 
 namespace {
@@ -518,10 +523,24 @@ struct RayBatch {
   bool on_device;
 };
 
-// cam and tiles, or (cam = tiles = nullptr) the ray batch rb
+// A pixel list in place of tiles (a round of rt_render_adaptive): entry j of `n` (0 < n < 2^31) is the pixel at
+// pixmap[j] (x | y << 16, device memory, as k_pixmap writes a tile list's), and slots[j] (null: j) is its place in
+// the records at `acc`. render() takes the list as its pixel map as it stands -- no tiles, no pixel_map() and none of
+// its cache -- and resolves every pass into the records' moments (launch_resolve_moments) instead of an image: there
+// is no `out`. prm->samples_per_item is the batch, prm->spp a multiple of it.
+struct PixelList {
+  const uint32_t* pixmap;
+  const uint32_t* slots;
+  uint32_t n;
+  AdaptiveAcc* acc;
+};
+
+// cam and tiles, or (cam = tiles = nullptr) the ray batch rb, or cam and (tiles = out = nullptr, out_dev = 1) the
+// pixel list pl
 template <class R>
 rt_status render(rt_context* c, const rt_camera_desc* cam, const rt_render_params* prm, const rt_tile* tiles,
-                 int32_t ntiles, void* out, int32_t out_dev, hipStream_t st, const RayBatch* rb = nullptr) {
+                 int32_t ntiles, void* out, int32_t out_dev, hipStream_t st, const RayBatch* rb = nullptr,
+                 const PixelList* pl = nullptr) {
   const bool f64 = sizeof(R) == 8;
   const CompiledScene& cs = c->scene;
   const SceneHeader& hdr = f64 ? cs.hdr64 : cs.hdr;
@@ -532,8 +551,8 @@ rt_status render(rt_context* c, const rt_camera_desc* cam, const rt_render_param
   if ((s = scene_to_device(c, f64, st, &lq)) != RT_OK) return s;
 
   // pixel map: tiles packed in order, row-major inside each tile (expanded by k_pixmap)
-  uint64_t npix64 = rb ? rb->n : 0;
-  const std::vector<uint4> tl = rb ? std::vector<uint4>() : pack_tiles(tiles, ntiles, npix64);
+  uint64_t npix64 = rb ? rb->n : pl ? pl->n : 0;
+  const std::vector<uint4> tl = (rb || pl) ? std::vector<uint4>() : pack_tiles(tiles, ntiles, npix64);
   if (npix64 >= (1ull << 31)) return set_err(c, RT_ERR_INVALID_ARGUMENT, "too many pixels in one call");
   const uint32_t npix = (uint32_t)npix64;
   if (npix == 0) return RT_OK;
@@ -544,7 +563,14 @@ rt_status render(rt_context* c, const rt_camera_desc* cam, const rt_render_param
     dout = c->out_tmp.ptr;
   }
 
-  if (prm->max_depth <= 0) {  // ray_color(r, 0) is black for every sample (camera.h:194-195)
+  if (prm->max_depth <= 0 && pl) {  // ... so the batches' sums are zero: the records count them and stay as they are
+    launch_resolve_moments<R>(nullptr, pl->slots, npix, (uint32_t)(prm->spp / prm->samples_per_item), pl->acc, st);
+    c->last.launches++;
+    RT_HIP(c, hipGetLastError());
+    c->pending = true;
+    c->pend_stream = st;
+    c->last.samples += (uint64_t)npix * (uint32_t)prm->spp;
+  } else if (prm->max_depth <= 0) {  // ray_color(r, 0) is black for every sample (camera.h:194-195)
     launch_zero<R>((R*)dout, (uint64_t)out_elems, st);
   } else {
     const uint32_t spp = (uint32_t)prm->spp;
@@ -581,7 +607,7 @@ rt_status render(rt_context* c, const rt_camera_desc* cam, const rt_render_param
     c->last.passes += plan.passes;
     c->last.partial_bytes = plan.partial_bytes;
     if ((s = ensure(c, c->blk, 4ull * (nblk_max + 2))) != RT_OK) return s;
-    if (!rb && (s = pixel_map(c, tl, npix, st)) != RT_OK) return s;
+    if (!rb && !pl && (s = pixel_map(c, tl, npix, st)) != RT_OK) return s;
 
     unsigned char* sp = (unsigned char*)c->state.ptr;
     LaunchParams<R> p{};
@@ -597,7 +623,7 @@ rt_status render(rt_context* c, const rt_camera_desc* cam, const rt_render_param
     p.S = (uint4*)(sp + 5 * r4);
     p.X = (uint4*)(sp + 5 * r4 + sb);
     p.partial = (R*)c->partial.ptr;
-    p.pixmap = (const uint32_t*)c->pixmap.ptr;
+    p.pixmap = pl ? pl->pixmap : (const uint32_t*)c->pixmap.ptr;
     p.queue = nullptr;
     p.n = P;
     p.P = P;
@@ -640,7 +666,8 @@ rt_status render(rt_context* c, const rt_camera_desc* cam, const rt_render_param
     // the launch lanes (rt_plan.h lane_plan): asked per launch, so the passes of a call alternate too
     // A ray batch stays on the caller's stream: its rays are the caller's, written on that stream, and a lane would
     // have to wait for them before every launch -- there is no unchanged-input case for the lanes to overlap.
-    lq.knob = env_frame_overlap() && !rb;
+    // A pixel list stays there too: the list is written on that stream just before, and the host waits between rounds.
+    lq.knob = env_frame_overlap() && !rb && !pl;
     lq.device_out = out_dev != 0;
     lq.persist = persist;
     lq.shared_scratch = p.sc.wide_spill != nullptr;
@@ -709,7 +736,10 @@ rt_status render(rt_context* c, const rt_camera_desc* cam, const rt_render_param
         s = persist ? run_persistent(c, p, kind, nblk_max, st) : run_wavefront(c, p, kind, nblk_max, st);
         if (s != RT_OK) return s;
       }
-      launch_resolve<R>(partial, npix, pc, spp, (R*)dout, c0 == 0, c0 + pc >= plan.nchunks, st);
+      if (pl)
+        launch_resolve_moments<R>(partial, pl->slots, npix, pc, pl->acc, st);
+      else
+        launch_resolve<R>(partial, npix, pc, spp, (R*)dout, c0 == 0, c0 + pc >= plan.nchunks, st);
       if (lp.overlap) RT_HIP(c, hipEventRecord(c->ev_resolved[lp.set], st));
       c->last.launches++;
       RT_HIP(c, hipGetLastError());
@@ -928,6 +958,90 @@ rt_status render_aov(rt_context* c, const rt_camera_desc* cam, const rt_aov_para
   return query_done(c, st, true, prm->on_device != 0, {{feat, p.feat, 64ull * npix}, {ids, p.ids, 16ull * npix}});
 }
 
+// ---------------------------------------------------------------- adaptive sampling
+// rt_render_adaptive for one precision: the round loop around render()'s pixel-list source. The tiles' pixel map is
+// expanded once, into c->pixmap like any render's (so it stays the cached map of these tiles), and is round 0's list;
+// the later rounds' lists are the select's survivors, in ad_pix / ad_slot, alternating. Every round: render() the
+// list's next samples into the moment records, select (estimate, decision, outputs of the pixels that stop, the next
+// list), and -- unless the round was the last there can be -- read the survivor count back and go on while it is not 0.
+template <class R>
+rt_status render_adaptive(rt_context* c, const rt_camera_desc* cam, const rt_adaptive_params* prm,
+                          const std::vector<uint4>& tl, uint32_t npix, void* out_rgb, int32_t* out_spp, double* out_err,
+                          hipStream_t st) {
+  const bool f64 = sizeof(R) == 8;
+  const auto t0 = std::chrono::steady_clock::now();
+  const PathKernel kind = path_kernel(f64 ? c->scene.hdr64 : c->scene.hdr, sizeof(typename WWord<R>::T), cam->mode, true,
+                                      prm->traversal == RT_TRAV_ORDERED, c->scene.stack_need);
+  if (prm->max_depth > 0 && !family_built(kind.fam))  // (render() would say so too, after the records were cleared)
+    return set_err(c, RT_ERR_UNSUPPORTED,
+                   std::string("this build (RT_DEV_ONLY) has no ") + family_name(kind.fam) + " kernels");
+  rt_status s;
+  if ((s = wait_other_stream(c, st)) != RT_OK) return s;  // (the call writes the context's buffers from here on)
+  const uint32_t nb = (npix + kBlock - 1) / kBlock;
+  const bool rounds = prm->min_spp < prm->max_spp;
+  if ((s = ensure(c, c->ad_acc, sizeof(AdaptiveAcc) * (size_t)npix)) != RT_OK) return s;
+  if ((s = ensure(c, c->ad_blk, 4ull * (nb + 2))) != RT_OK) return s;
+  for (int k = 0; rounds && k < 2; k++) {
+    if ((s = ensure(c, c->ad_pix[k], 4ull * npix)) != RT_OK) return s;
+    if ((s = ensure(c, c->ad_slot[k], 4ull * npix)) != RT_OK) return s;
+  }
+  SelectParams sp{};
+  sp.out_rgb = out_rgb;
+  sp.out_spp = out_spp;
+  sp.out_err = out_err;
+  if (!prm->on_device) {
+    if ((s = stage(c, c->out_tmp, 3 * sizeof(R) * (size_t)npix, sp.out_rgb)) != RT_OK) return s;
+    if ((s = stage(c, c->ad_spp, 4ull * npix, sp.out_spp)) != RT_OK) return s;
+    if ((s = stage(c, c->ad_err, 8ull * npix, sp.out_err)) != RT_OK) return s;
+  }
+  if ((s = pixel_map(c, tl, npix, st)) != RT_OK) return s;
+  c->pending = true;  // outstanding from here on, whatever fails below
+  c->pend_stream = st;
+  RT_HIP(c, hipMemsetAsync(c->ad_acc.ptr, 0, sizeof(AdaptiveAcc) * (size_t)npix, st));
+  sp.acc = (AdaptiveAcc*)c->ad_acc.ptr;
+  sp.blk = (uint32_t*)c->ad_blk.ptr;
+  sp.batch = (uint32_t)prm->batch;
+  sp.max_spp = (uint32_t)prm->max_spp;
+  sp.threshold = prm->threshold;
+  sp.floor = prm->floor;
+  // a round's render: the persistent schedule (no segments_per_launch), the automatic grid, an item a batch
+  rt_render_params rp{};
+  rp.max_depth = prm->max_depth;
+  rp.seed = prm->seed;
+  rp.precision = prm->precision;
+  rp.samples_per_item = prm->batch;
+  rp.traversal = prm->traversal;
+  PixelList pl{(const uint32_t*)c->pixmap.ptr, nullptr, npix, sp.acc};
+  int next = 0;
+  for (int32_t have = 0;;) {
+    rp.spp = have == 0 ? prm->min_spp : prm->step_spp;
+    rp.first_sample = have;
+    if ((s = render<R>(c, cam, &rp, nullptr, 0, nullptr, 1, st, nullptr, &pl)) != RT_OK) return s;
+    have += rp.spp;
+    const bool last = have >= prm->max_spp;  // every pixel stops after this round: no next list, no count to wait for
+    sp.pixmap = pl.pixmap;
+    sp.slots = pl.slots;
+    sp.n = pl.n;
+    sp.next_pixmap = last ? nullptr : (uint32_t*)c->ad_pix[next].ptr;
+    sp.next_slots = last ? nullptr : (uint32_t*)c->ad_slot[next].ptr;
+    launch_adaptive_select<R>(sp, st);
+    c->last.launches += last ? 1 : 3;
+    RT_HIP(c, hipGetLastError());
+    if (last) break;
+    RT_HIP(c, hipMemcpyAsync(c->total_host, sp.blk + (pl.n + kBlock - 1) / kBlock + 1, 4, hipMemcpyDeviceToHost, st));
+    RT_HIP(c, hipStreamSynchronize(st));
+    const uint32_t alive = *c->total_host;
+    if (alive == 0) break;
+    pl = PixelList{sp.next_pixmap, sp.next_slots, alive, sp.acc};
+    next ^= 1;
+  }
+  c->last.last_render_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return query_done(c, st, false, prm->on_device != 0,
+                    {{out_rgb, sp.out_rgb, 3 * sizeof(R) * (size_t)npix},
+                     {out_spp, sp.out_spp, 4ull * npix},
+                     {out_err, sp.out_err, 8ull * npix}});
+}
+
 // ---------------------------------------------------------------- argument checks of the C entry points
 // Each check is written once; every entry point calls the ones it has in its own order (which error wins when several
 // apply differs between them, and stays: tests/test_gpu_query_contract.py).
@@ -1075,7 +1189,8 @@ void rt_context_destroy(rt_context* c) {
   if (c->lane1) (void)hipStreamDestroy(c->lane1);
   for (DevBuf* b : {&c->partial2, &c->heads2, &c->scene32, &c->scene64, &c->state, &c->partial, &c->pixmap, &c->queue0, &c->queue1, &c->blk, &c->wide_spill,
                     &c->out_tmp, &c->counters, &c->camx, &c->heads, &c->tiles, &c->fault, &c->ids, &c->q_rays, &c->q_geom,
-                    &c->q_ids})
+                    &c->q_ids, &c->ad_acc, &c->ad_pix[0], &c->ad_pix[1], &c->ad_slot[0], &c->ad_slot[1], &c->ad_blk,
+                    &c->ad_spp, &c->ad_err})
     if (b->ptr) (void)hipFree(b->ptr);
   for (hipEvent_t e : c->events) (void)hipEventDestroy(e);
   if (c->total_host) (void)hipHostFree(c->total_host);
@@ -1275,6 +1390,42 @@ rt_status rt_render_aov(rt_context* c, const rt_camera_desc* cam, const rt_aov_p
     hipStream_t st = call_stream(c, stream, prm->on_device != 0);
     return render_aov<decltype(r)>(c, cam, prm, tl, (uint32_t)npix, out_feat, out_ids, st);
   });
+}
+
+rt_status rt_adaptive_check(const rt_adaptive_params* prm, char* err, int32_t errlen) {
+  const char* m = prm ? adaptive_params_error(*prm) : "null parameters";
+  if (err && errlen > 0) std::snprintf(err, (size_t)errlen, "%s", m ? m : "");
+  return m ? RT_ERR_INVALID_ARGUMENT : RT_OK;
+}
+
+rt_status rt_render_adaptive(rt_context* c, const rt_camera_desc* cam, const rt_adaptive_params* prm,
+                             const rt_tile* tiles, int32_t ntiles, void* out_rgb, int32_t* out_spp, double* out_err,
+                             void* stream) {
+  if (!c) return set_err(nullptr, RT_ERR_INVALID_ARGUMENT, "null context");
+  if (!cam || !prm || (!tiles && ntiles > 0) || ntiles < 0 || !out_rgb || !out_spp || !out_err)
+    return set_err(c, RT_ERR_INVALID_ARGUMENT, "null argument");
+  if (const char* m = adaptive_params_error(*prm)) return set_err(c, RT_ERR_INVALID_ARGUMENT, m);
+  if (prm->on_device && ((uintptr_t)out_rgb | (uintptr_t)out_spp | (uintptr_t)out_err) % 16 != 0)
+    return set_err(c, RT_ERR_INVALID_ARGUMENT, "device out_rgb, out_spp and out_err must be 16-byte aligned");
+  rt_status s;
+  if ((s = check_camera(c, cam)) != RT_OK) return s;
+  if ((s = check_tiles(c, cam, tiles, ntiles)) != RT_OK) return s;
+  if ((s = check_scene(c)) != RT_OK) return s;
+  return by_precision(c, prm->precision, true, [&](auto r) -> rt_status {
+    uint64_t npix = 0;
+    const std::vector<uint4> tl = pack_tiles(tiles, ntiles, npix);
+    if (npix >= (1ull << 31)) return set_err(c, RT_ERR_INVALID_ARGUMENT, "too many pixels in one call");
+    if (npix == 0) return RT_OK;
+    RT_HIP(c, hipSetDevice(c->device));
+    hipStream_t st = call_stream(c, stream, prm->on_device != 0);
+    return render_adaptive<decltype(r)>(c, cam, prm, tl, (uint32_t)npix, out_rgb, out_spp, out_err, st);
+  });
+}
+
+// The estimator as the kernel runs it (rt_plan.h adaptive_error), for tests: no device, no stability promise.
+void rt_dev_adaptive_error(int32_t K, int32_t batch, const double* S, const double* Q, double floor, double* mean3,
+                           double* err) {
+  adaptive_error((uint32_t)K, (uint32_t)batch, S, Q, floor, mean3, err);
 }
 
 int32_t rt_trace_family(rt_context* c, int32_t precision, int32_t traversal) {

@@ -101,6 +101,12 @@ class rt_radiance_params(ctypes.Structure):
                 ("on_device", c_int32)]
 
 
+class rt_adaptive_params(ctypes.Structure):
+    _fields_ = [("seed", c_uint64), ("min_spp", c_int32), ("max_spp", c_int32), ("step_spp", c_int32),
+                ("batch", c_int32), ("max_depth", c_int32), ("precision", c_int32), ("traversal", c_int32),
+                ("on_device", c_int32), ("threshold", c_double), ("floor", c_double)]
+
+
 # rt_trace_family_kind
 RT_TRACE_FLAT, RT_TRACE_LINEAR, RT_TRACE_WIDE_LDS, RT_TRACE_WIDE_HBM, RT_TRACE_STACK = range(5)
 TRACE_FAMILY_NAMES = ("FLAT", "LINEAR", "WIDE_LDS", "WIDE_HBM", "STACK")
@@ -133,6 +139,13 @@ SIGNATURES = {
                                  ctypes.POINTER(rt_tile), c_int32, ctypes.c_void_p, c_int32, ctypes.c_void_p]),
     "rt_render_aov": (c_int32, [ctypes.c_void_p, ctypes.POINTER(rt_camera_desc), ctypes.POINTER(rt_aov_params),
                                 ctypes.POINTER(rt_tile), c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "rt_render_adaptive": (c_int32, [ctypes.c_void_p, ctypes.POINTER(rt_camera_desc),
+                                     ctypes.POINTER(rt_adaptive_params), ctypes.POINTER(rt_tile), c_int32,
+                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "rt_adaptive_check": (c_int32, [ctypes.POINTER(rt_adaptive_params), ctypes.c_char_p, c_int32]),
+    # (a development helper the header declares: the estimator's arithmetic on the host)
+    "rt_dev_adaptive_error": (None, [c_int32, c_int32, ctypes.POINTER(c_double), ctypes.POINTER(c_double), c_double,
+                                     ctypes.POINTER(c_double), ctypes.POINTER(c_double)]),
     "rt_multi_create": (c_int32, [ctypes.POINTER(c_int32), c_int32, ctypes.POINTER(ctypes.c_void_p)]),
     "rt_multi_destroy": (None, [ctypes.c_void_p]),
     "rt_multi_last_error": (ctypes.c_char_p, [ctypes.c_void_p]),

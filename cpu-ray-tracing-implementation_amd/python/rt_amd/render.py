@@ -233,6 +233,29 @@ class Context:
         return dict(albedo=feat[:, 0:3].reshape(*shape, 3), normal=feat[:, 3:6].reshape(*shape, 3),
                     depth=feat[:, 6].reshape(*shape), hit=feat[:, 7].reshape(*shape), ids=ids.reshape(*shape, 4))
 
+    def render_adaptive(self, cam, max_spp, max_depth, threshold, min_spp=None, step_spp=None, batch=4, floor=0.01,
+                        seed=1, precision=abi.RT_PREC_F32, traversal=0, tiles=None, device=False, stream=None):
+        """An adaptively sampled frame with its noise map (rt_render_adaptive): dict(rgb (.., 3) of the precision's
+        dtype, spp (..) int32 the samples each pixel took, err (..) float64 its final error estimate). Every pixel takes
+        min_spp samples, then step_spp more per round until its estimated relative standard error is <= threshold or it
+        has max_spp; the estimate is the batch-means one over batches of `batch` samples (include/rt_hip.h). Defaults:
+        step_spp = 4 * batch, min_spp = step_spp. Shapes are (H, W, ..) for the whole image, (npix, ..) for given
+        tiles. device=False: numpy arrays, filled on return; device=True: torch tensors on the context's device, the
+        call ordered on `stream` (default torch's current stream)."""
+        step_spp = 4 * batch if step_spp is None else step_spp
+        min_spp = step_spp if min_spp is None else min_spp
+        arr, nt, npix, full = self._tiles(cam, tiles)
+        prm = abi.rt_adaptive_params(seed=seed, min_spp=min_spp, max_spp=max_spp, step_spp=step_spp, batch=batch,
+                                     max_depth=max_depth, precision=precision, traversal=traversal,
+                                     on_device=1 if device else 0, threshold=threshold, floor=floor)
+        dev, sp = self._output_device(device, stream)
+        rgb, rp = self._output(npix, (3,), "float64" if precision == abi.RT_PREC_F64 else "float32", dev, fill=0.0)
+        spp, np_ = self._output(npix, (), "int32", dev, fill=0)
+        err, ep = self._output(npix, (), "float64", dev, fill=0.0)
+        self._check(self.lib.rt_render_adaptive(self.h, ctypes.byref(cam), ctypes.byref(prm), arr, nt, rp, np_, ep, sp))
+        shape = (cam.image_height, cam.image_width) if full else (npix,)
+        return dict(rgb=rgb.reshape(*shape, 3), spp=spp.reshape(*shape), err=err.reshape(*shape))
+
     @staticmethod
     def _stream_handle(stream):
         return int(getattr(stream, "cuda_stream", stream) or 0)

@@ -461,6 +461,68 @@ typedef struct rt_aov_params {
 rt_status rt_render_aov(rt_context* ctx, const rt_camera_desc* cam, const rt_aov_params* params, const rt_tile* tiles,
                         int32_t ntiles, double* out_feat, int32_t* out_ids, void* stream);
 
+/* ---- adaptive sampling: a per-pixel noise estimate, and samples only where they still help ----
+ *
+ * rt_render_adaptive renders the tiles' pixels in rounds and stops each pixel once its estimated error is small
+ * enough. No reference counterpart: camera::render gives every pixel samples_per_pixel samples.
+ *
+ * Sampling. A pixel's samples come in batches of `batch` consecutive samples: batch k is samples
+ * [k * batch, (k + 1) * batch) of the key (seed, y * W + x), the samples rt_render_tiles draws for that pixel. The
+ * first round renders samples [0, min_spp) of every pixel; each later round the next step_spp samples of the pixels
+ * still active. A round is a render with samples_per_item = batch and first_sample = the samples the active pixels
+ * have, over the list of active pixels in place of tiles: an item is a batch, and chunk passes under the partial-sum
+ * budget apply as for a render.
+ *
+ * Estimator (the method of batch means). s_k: the three sums batch k's item wrote (floats or doubles, by the
+ * precision), converted to double. Per channel, in double and in batch order, S_c = sum s_k,c and Q_c = sum s_k,c^2
+ * over the K batches so far. With N = K * batch:
+ *   mean_c = S_c / N                                     (rounded once to the precision for out_rgb)
+ *   var_c  = max(0, Q_c - S_c^2 / K) / (K - 1)           (a NaN stays a NaN)
+ *   se2    = (var_r + var_g + var_b) / (K * batch^2)     the summed variance of the three channel means
+ *   err    = sqrt(se2 / 3) / (floor + (mean_r + mean_g + mean_b) / 3)
+ * err is the RMS standard error of the channels relative to the pixel's level; `floor` makes it absolute in dark
+ * pixels. A pixel stops after a round when err <= threshold or N >= max_spp. A NaN err fails the comparison, so such
+ * a pixel runs to max_spp. threshold = 0 takes every pixel with any variance to max_spp (a fixed-spp render with a
+ * noise map); threshold = +inf stops every pixel at min_spp. max_depth = 0 gives black pixels with err = 0 that stop
+ * at min_spp.
+ *
+ * Outputs, packed by tile exactly as rt_render_tiles packs them: out_rgb npix x 3 floats (RT_PREC_F32) or doubles
+ * (RT_PREC_F64), out_spp the samples each pixel took, out_err each pixel's final err. None may be NULL.
+ *
+ * A pixel's three outputs depend on (seed, pixel) and the parameters alone: not on the tiling, the tile order, the
+ * other pixels of the call, the partial-sum budget or the device. The image is bit-identical for any split of the
+ * frame. Only the persistent schedule is used, as for rt_radiance, and the kernel is the one a render of that scene
+ * and camera takes, unchanged.
+ *
+ * Stream and ordering. The host must know each round's count of active pixels: the call waits on `stream` once per
+ * round (a 4-byte read), but not after the last round when on_device = 1. The outputs are ordered on `stream` like a
+ * device-output render's, and the call joins the context's outstanding work the same way; its launches stay on
+ * `stream` (they do not overlap as consecutive frames do). */
+typedef struct rt_adaptive_params {
+  uint64_t seed;
+  int32_t min_spp, max_spp, step_spp, batch; /* batch >= 1; step_spp a multiple of batch; min_spp and max_spp
+                                                multiples of step_spp; 2 * batch <= min_spp <= max_spp */
+  int32_t max_depth;                         /* >= 0 */
+  int32_t precision;                         /* rt_precision */
+  int32_t traversal;                         /* rt_traversal */
+  int32_t on_device;         /* 1: the three outputs are device pointers (16-byte aligned), the call is stream-ordered */
+  double threshold, floor;   /* threshold >= 0 (+inf allowed), not NaN; floor > 0 and finite */
+} rt_adaptive_params;        /* 56 bytes, no padding */
+/* RT_ERR_INVALID_ARGUMENT: a null pointer, parameters that break the rules above (rt_adaptive_check), rt_render_tiles'
+ * errors for the camera and the tiles, device pointers (on_device = 1) not aligned to 16 bytes; RT_ERR_NO_SCENE;
+ * RT_ERR_UNSUPPORTED: a family a development build omits. On an error nothing is launched and nothing is written. No
+ * pixels: nothing is launched. Adds the sum of out_spp to rt_counters.samples; segments, launches and passes grow as
+ * the rounds' launches and resolves add them. */
+rt_status rt_render_adaptive(rt_context* ctx, const rt_camera_desc* cam, const rt_adaptive_params* params,
+                             const rt_tile* tiles, int32_t ntiles, void* out_rgb, int32_t* out_spp, double* out_err,
+                             void* stream);
+/* The parameter rules alone, on the host (no device): RT_OK, or RT_ERR_INVALID_ARGUMENT with the message in err. */
+rt_status rt_adaptive_check(const rt_adaptive_params* params, char* err, int32_t errlen);
+/* The estimator's arithmetic as the kernel runs it, on the host, for tests: from K batches of `batch` samples with the
+ * sums S[3] and Q[3] to mean3[3] (in double) and *err. A development helper with no stability promise. */
+void rt_dev_adaptive_error(int32_t K, int32_t batch, const double* S, const double* Q, double floor, double* mean3,
+                           double* err);
+
 /* ---- multi-GPU driver: the framebuffer tiled over the devices of one node ----
  *
  * Replaces camera::render's per-row std::for_each(par_unseq) (camera.h:154-172) when a
