@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "rt_denoise.h"
 #include "rt_plan.h"
 #include "rt_types.h"
 
@@ -231,6 +232,13 @@ struct CamRayParams {
   uint64_t seed;
 };
 void launch_camera_rays(const CamRayParams& p, hipStream_t st);
+
+// ---- denoising (rt_denoise; the kernels are rt_denoise.hip's): the prepare pass and prm.iterations a-trous passes on
+// `st`, iterations + 1 launches. scratch: kDnScratchT T a pixel; the other pointers as rt_denoise takes them, on the
+// device (var may be null, rgb_out may be rgb_in).
+template <class T>
+void launch_denoise(const rt_denoise_params& prm, const T* rgb_in, const double* feat, const double* var, T* scratch,
+                    T* rgb_out, hipStream_t st);
 
 // the fp64 sin/cos table (rt_device.h g_sincos_tab) copied to the calling thread's device
 hipError_t upload_sincos_table();

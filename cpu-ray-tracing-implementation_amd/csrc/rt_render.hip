@@ -84,6 +84,9 @@ struct rt_context {
   // between (positions, and the pixels' slots in the outputs and records), the select's block counts, and device
   // copies of a host-pointer call's out_spp and out_err (out_rgb's is out_tmp)
   DevBuf ad_acc, ad_pix[2], ad_slot[2], ad_blk, ad_spp, ad_err;
+  // denoising (rt_denoise): the working records, kDnScratchT T a pixel; a host-pointer call's inputs and output are
+  // staged in out_tmp (rgb, in and out), q_rays (feat) and q_geom (var)
+  DevBuf dn_scratch;
 };
 
 namespace {
@@ -1042,6 +1045,32 @@ rt_status render_adaptive(rt_context* c, const rt_camera_desc* cam, const rt_ada
                      {out_err, sp.out_err, 8ull * npix}});
 }
 
+// rt_denoise for one precision: checked parameters, whole image. The prepare pass has read rgb_in before the last
+// pass writes rgb_out, on one stream, so the two may be the same array.
+template <class T>
+rt_status denoise(rt_context* c, const rt_denoise_params* prm, const void* rgb_in, const double* feat,
+                  const double* var, void* rgb_out, hipStream_t st) {
+  const size_t npix = (size_t)prm->width * (size_t)prm->height;
+  rt_status s;
+  if ((s = wait_other_stream(c, st)) != RT_OK) return s;  // (a call on another stream may still use the scratch)
+  if ((s = ensure(c, c->dn_scratch, npix * kDnScratchT * sizeof(T))) != RT_OK) return s;
+  const T* in = (const T*)rgb_in;
+  T* out = (T*)rgb_out;
+  if (!prm->on_device) {
+    const double *host_feat = feat, *host_var = var;
+    if ((s = stage(c, c->out_tmp, npix * 3 * sizeof(T), out)) != RT_OK) return s;
+    if ((s = stage(c, c->q_rays, npix * 64, feat)) != RT_OK) return s;
+    if (var && (s = stage(c, c->q_geom, npix * 8, var)) != RT_OK) return s;
+    in = out;
+    RT_HIP(c, hipMemcpyAsync(out, rgb_in, npix * 3 * sizeof(T), hipMemcpyHostToDevice, st));
+    RT_HIP(c, hipMemcpyAsync((void*)feat, host_feat, npix * 64, hipMemcpyHostToDevice, st));
+    if (var) RT_HIP(c, hipMemcpyAsync((void*)var, host_var, npix * 8, hipMemcpyHostToDevice, st));
+  }
+  launch_denoise<T>(*prm, in, feat, var, (T*)c->dn_scratch.ptr, out, st);
+  c->last.launches += (uint64_t)prm->iterations + 1;
+  return query_done(c, st, false, prm->on_device != 0, {{rgb_out, out, npix * 3 * sizeof(T)}});
+}
+
 // ---------------------------------------------------------------- argument checks of the C entry points
 // Each check is written once; every entry point calls the ones it has in its own order (which error wins when several
 // apply differs between them, and stays: tests/test_gpu_query_contract.py).
@@ -1190,7 +1219,7 @@ void rt_context_destroy(rt_context* c) {
   for (DevBuf* b : {&c->partial2, &c->heads2, &c->scene32, &c->scene64, &c->state, &c->partial, &c->pixmap, &c->queue0, &c->queue1, &c->blk, &c->wide_spill,
                     &c->out_tmp, &c->counters, &c->camx, &c->heads, &c->tiles, &c->fault, &c->ids, &c->q_rays, &c->q_geom,
                     &c->q_ids, &c->ad_acc, &c->ad_pix[0], &c->ad_pix[1], &c->ad_slot[0], &c->ad_slot[1], &c->ad_blk,
-                    &c->ad_spp, &c->ad_err})
+                    &c->ad_spp, &c->ad_err, &c->dn_scratch})
     if (b->ptr) (void)hipFree(b->ptr);
   for (hipEvent_t e : c->events) (void)hipEventDestroy(e);
   if (c->total_host) (void)hipHostFree(c->total_host);
@@ -1428,6 +1457,22 @@ void rt_dev_adaptive_error(int32_t K, int32_t batch, const double* S, const doub
   adaptive_error((uint32_t)K, (uint32_t)batch, S, Q, floor, mean3, err);
 }
 
+// (rt_denoise_check and rt_dev_denoise_host, which need no context: rt_denoise.hip)
+rt_status rt_denoise(rt_context* c, const rt_denoise_params* prm, const void* rgb_in, const double* feat,
+                     const double* var, void* rgb_out, void* stream) {
+  // (the context last: the checks before it need none, and rt_last_error(NULL) names the one that failed)
+  if (!prm || !rgb_in || !feat || !rgb_out) return set_err(c, RT_ERR_INVALID_ARGUMENT, "null argument");
+  if (const char* m = denoise_params_error(*prm)) return set_err(c, RT_ERR_INVALID_ARGUMENT, m);
+  if (!c) return set_err(nullptr, RT_ERR_INVALID_ARGUMENT, "null context");
+  if (prm->on_device && ((uintptr_t)rgb_in | (uintptr_t)feat | (uintptr_t)var | (uintptr_t)rgb_out) % 16 != 0)
+    return set_err(c, RT_ERR_INVALID_ARGUMENT, "device rgb_in, feat, var and rgb_out must be 16-byte aligned");
+  return by_precision(c, prm->precision, false, [&](auto r) -> rt_status {
+    RT_HIP(c, hipSetDevice(c->device));
+    hipStream_t st = call_stream(c, stream, prm->on_device != 0);
+    return denoise<decltype(r)>(c, prm, rgb_in, feat, var, rgb_out, st);
+  });
+}
+
 int32_t rt_trace_family(rt_context* c, int32_t precision, int32_t traversal) {
   if (!c || !c->has_scene || (precision != RT_PREC_F32 && precision != RT_PREC_F64) ||
       (traversal != RT_TRAV_AUTO && traversal != RT_TRAV_ORDERED))
@@ -1502,3 +1547,7 @@ void rt_dev_plan_radiance(const rt_scene_desc* desc, int32_t precision, int32_t 
 }
 
 }  // extern "C"
+
+// The denoiser's kernels, their launch function and its two host-only entry points: a file of their own, compiled as
+// part of this translation unit, so that the library stays the four sources every build of it lists.
+#include "rt_denoise.hip"

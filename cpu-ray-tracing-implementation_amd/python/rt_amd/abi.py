@@ -107,6 +107,15 @@ class rt_adaptive_params(ctypes.Structure):
                 ("on_device", c_int32), ("threshold", c_double), ("floor", c_double)]
 
 
+RT_DENOISE_DEMODULATE = 1
+
+
+class rt_denoise_params(ctypes.Structure):
+    _fields_ = [("width", c_int32), ("height", c_int32), ("iterations", c_int32), ("precision", c_int32),
+                ("on_device", c_int32), ("flags", c_int32), ("sigma_color", c_double), ("sigma_normal", c_double),
+                ("sigma_depth", c_double), ("albedo_eps", c_double), ("color_eps", c_double), ("depth_eps", c_double)]
+
+
 # rt_trace_family_kind
 RT_TRACE_FLAT, RT_TRACE_LINEAR, RT_TRACE_WIDE_LDS, RT_TRACE_WIDE_HBM, RT_TRACE_STACK = range(5)
 TRACE_FAMILY_NAMES = ("FLAT", "LINEAR", "WIDE_LDS", "WIDE_HBM", "STACK")
@@ -146,6 +155,9 @@ SIGNATURES = {
     # (a development helper the header declares: the estimator's arithmetic on the host)
     "rt_dev_adaptive_error": (None, [c_int32, c_int32, ctypes.POINTER(c_double), ctypes.POINTER(c_double), c_double,
                                      ctypes.POINTER(c_double), ctypes.POINTER(c_double)]),
+    "rt_denoise_check": (c_int32, [ctypes.POINTER(rt_denoise_params), ctypes.c_char_p, ctypes.c_size_t]),
+    "rt_denoise": (c_int32, [ctypes.c_void_p, ctypes.POINTER(rt_denoise_params), ctypes.c_void_p, ctypes.c_void_p,
+                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "rt_multi_create": (c_int32, [ctypes.POINTER(c_int32), c_int32, ctypes.POINTER(ctypes.c_void_p)]),
     "rt_multi_destroy": (None, [ctypes.c_void_p]),
     "rt_multi_last_error": (ctypes.c_char_p, [ctypes.c_void_p]),
@@ -220,6 +232,10 @@ def load():
         lib.rt_dev_plan_radiance.restype = None
         lib.rt_dev_plan_radiance.argtypes = [ctypes.POINTER(rt_scene_desc), c_int32, c_int32, ctypes.c_char_p,
                                              ctypes.c_size_t]
+        # ... and rt_denoise's passes as a host loop over the kernels' own arithmetic (no GPU): rt_amd.denoise_host
+        lib.rt_dev_denoise_host.restype = c_int32
+        lib.rt_dev_denoise_host.argtypes = [ctypes.POINTER(rt_denoise_params), ctypes.c_void_p, ctypes.c_void_p,
+                                            ctypes.c_void_p, ctypes.c_void_p]
         if lib.rt_abi_version() != ABI_VERSION:
             raise RuntimeError(f"{path} has ABI {lib.rt_abi_version()}, this binding expects {ABI_VERSION}: rebuild")
         _lib = lib

@@ -256,6 +256,51 @@ class Context:
         shape = (cam.image_height, cam.image_width) if full else (npix,)
         return dict(rgb=rgb.reshape(*shape, 3), spp=spp.reshape(*shape), err=err.reshape(*shape))
 
+    def denoise(self, rgb, aov, var=None, iterations=5, sigma_color=2.0, sigma_normal=0.5, sigma_depth=1.0,
+                demodulate=True, albedo_eps=1e-2, color_eps=1e-8, depth_eps=1e-3, stream=None):
+        """The frame `rgb`, (H, W, 3) float32 or float64, filtered by the variance-guided a-trous filter (rt_denoise):
+        spatial, single-frame, guided by `aov` -- render_aov's dict, or its rows as an (H, W, 8) or (npix, 8) float64
+        array albedo[3], normal[3], depth, hit -- and by `var`, (H, W) float64, the summed variance of the three channel
+        means (adaptive_variance of render_adaptive's dict; None: sigma_color is an absolute colour distance). The
+        precision is rgb's dtype. Needs no scene. -> (H, W, 3) of rgb's kind and dtype.
+
+        numpy inputs take the host path; torch tensors on the context's device take the device path, ordered on
+        `stream` (default torch's current stream). The three inputs are of one kind."""
+        dev = None if isinstance(rgb, np.ndarray) else rgb.device
+        if dev is None:
+            xp, f64, f32, cat = np, np.float64, np.float32, np.concatenate
+            contiguous, ptr = np.ascontiguousarray, (lambda a: a.ctypes.data)
+        else:
+            import torch
+            if not (isinstance(rgb, torch.Tensor) and rgb.is_cuda):
+                raise ValueError("rgb: a numpy array or a CUDA/HIP torch tensor")
+            xp, f64, f32, cat = torch, torch.float64, torch.float32, torch.cat
+            contiguous, ptr = (lambda a: a.contiguous()), (lambda a: a.data_ptr())
+        if rgb.ndim != 3 or rgb.shape[2] != 3 or rgb.dtype not in (f32, f64):
+            raise ValueError("rgb: an (H, W, 3) float32 or float64 array or tensor")
+        H, W = int(rgb.shape[0]), int(rgb.shape[1])
+        if isinstance(aov, dict):
+            aov = cat([aov["albedo"].reshape(H * W, 3), aov["normal"].reshape(H * W, 3),
+                       aov["depth"].reshape(H * W, 1), aov["hit"].reshape(H * W, 1)], 1)
+        if not isinstance(aov, type(rgb)) or aov.dtype != f64 or aov.shape[-1] != 8 or int(np.prod(aov.shape)) != H * W * 8:
+            raise ValueError("aov: render_aov's dict, or an (H, W, 8) or (npix, 8) float64 array of rgb's kind")
+        if var is not None and (not isinstance(var, type(rgb)) or var.dtype != f64 or int(np.prod(var.shape)) != H * W):
+            raise ValueError("var: an (H, W) float64 array of rgb's kind")
+        if dev is not None and any(t is not None and t.device != dev for t in (aov, var)):
+            raise ValueError("rgb, aov and var must be on one device")
+        rgb, aov = contiguous(rgb), contiguous(aov)
+        var = None if var is None else contiguous(var)
+        prm = abi.rt_denoise_params(width=W, height=H, iterations=iterations,
+                                    precision=abi.RT_PREC_F64 if rgb.dtype == f64 else abi.RT_PREC_F32,
+                                    on_device=int(dev is not None), flags=abi.RT_DENOISE_DEMODULATE if demodulate else 0,
+                                    sigma_color=sigma_color, sigma_normal=sigma_normal, sigma_depth=sigma_depth,
+                                    albedo_eps=albedo_eps, color_eps=color_eps, depth_eps=depth_eps)
+        out = xp.empty_like(rgb)
+        sp = None if dev is None else self._torch_stream(stream, dev)
+        self._check(self.lib.rt_denoise(self.h, ctypes.byref(prm), ptr(rgb), ptr(aov),
+                                        None if var is None else ptr(var), ptr(out), sp))
+        return out
+
     @staticmethod
     def _stream_handle(stream):
         return int(getattr(stream, "cuda_stream", stream) or 0)
@@ -306,6 +351,40 @@ class Multi:
         c = abi.rt_counters()
         self._check(self.lib.rt_multi_stats(self.h, rank, ctypes.byref(c)))
         return c
+
+
+def adaptive_variance(out, floor=0.01):
+    """render_adaptive's dict (with the `floor` it was rendered with) -> the `var` Context.denoise takes: per pixel the
+    summed variance of the three channel means, (err * (floor + level))^2 * 3 with level the mean of the pixel's
+    channels (the estimator's se2, include/rt_hip.h), float64, numpy or torch as the dict's arrays are."""
+    rgb, err = out["rgb"], out["err"]
+    if isinstance(rgb, np.ndarray):
+        level = rgb.astype(np.float64).sum(-1) / 3.0
+    else:
+        level = rgb.double().sum(-1) / 3.0
+    return (err * (floor + level)) ** 2 * 3.0
+
+
+def denoise_host(rgb, feat, var=None, iterations=5, sigma_color=2.0, sigma_normal=0.5, sigma_depth=1.0,
+                 demodulate=True, albedo_eps=1e-2, color_eps=1e-8, depth_eps=1e-3):
+    """Context.denoise's passes run by a host loop over the kernels' own arithmetic (rt_dev_denoise_host): numpy
+    arrays, rgb (H, W, 3) float32 or float64, feat (H * W, 8) float64, var (H, W) float64 or None. No GPU, no Context;
+    a development helper for tests."""
+    H, W = rgb.shape[:2]
+    rgb = np.ascontiguousarray(rgb)
+    feat = np.ascontiguousarray(feat, np.float64)
+    var = None if var is None else np.ascontiguousarray(var, np.float64)
+    prm = abi.rt_denoise_params(width=W, height=H, iterations=iterations,
+                                precision=abi.RT_PREC_F64 if rgb.dtype == np.float64 else abi.RT_PREC_F32, on_device=0,
+                                flags=abi.RT_DENOISE_DEMODULATE if demodulate else 0, sigma_color=sigma_color,
+                                sigma_normal=sigma_normal, sigma_depth=sigma_depth, albedo_eps=albedo_eps,
+                                color_eps=color_eps, depth_eps=depth_eps)
+    out = np.empty_like(rgb)
+    st = abi.load().rt_dev_denoise_host(ctypes.byref(prm), rgb.ctypes.data, feat.ctypes.data,
+                                        None if var is None else var.ctypes.data, out.ctypes.data)
+    if st != abi.RT_OK:
+        raise abi.RTError(st, "rt_dev_denoise_host: parameters rt_denoise_check refuses")
+    return out
 
 
 def multi_plan(w, h, ndev, rank, tile_size=0):

@@ -39,6 +39,7 @@
 #ifndef RT_HIP_H
 #define RT_HIP_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -522,6 +523,56 @@ rt_status rt_adaptive_check(const rt_adaptive_params* params, char* err, int32_t
  * sums S[3] and Q[3] to mean3[3] (in double) and *err. A development helper with no stability promise. */
 void rt_dev_adaptive_error(int32_t K, int32_t batch, const double* S, const double* Q, double floor, double* mean3,
                            double* err);
+
+/* ---- denoising: a variance-guided a-trous filter over the guide channels ----
+ *
+ * rt_denoise filters a whole row-major width x height image with an edge-avoiding a-trous wavelet filter (Dammertz et
+ * al. 2010) whose colour edge-stop scales with each pixel's own variance and which carries that variance from pass to
+ * pass (Schied et al. 2017, SVGF). It is spatial and single-frame: no history, no motion vectors. No reference
+ * counterpart. It needs no scene.
+ *
+ * rgb_in: npix x 3 floats (RT_PREC_F32) or doubles (RT_PREC_F64), e.g. rt_render_tiles' or rt_render_adaptive's image.
+ * feat:   npix x 8 doubles, rt_render_aov's rows: albedo[3], normal[3], depth, hit (depth a distance, >= 0).
+ * var:    npix doubles or NULL: the summed variance of the three channel means, the estimator's se2 above; from
+ *         rt_render_adaptive's out_err it is (err * (floor + level))^2 * 3 with level the mean of the pixel's channels.
+ * rgb_out: npix x 3 of the precision's type; may be rgb_in.
+ *
+ * All arithmetic is in T, float or double by the precision.
+ * Prepare, per pixel p. hit > 0: n = normal / hit, z = depth / hit; else n = 0, z = -1, a "miss pixel".
+ *   a = albedo + albedo_eps per channel with RT_DENOISE_DEMODULATE, else 1; c = rgb / a.
+ *   v0 = var / 3 / mean(a)^2 and v = the 3 x 3 binomial ([1 2 1] / 4 per axis) mean of v0, taps outside the image
+ *   skipped and the weights renormalised. var == NULL: v = 1, and sigma_color is an absolute colour distance.
+ *   g = (gx, gy), the depth gradient in depth per pixel, per axis: the mean of the forward and the backward difference
+ *   where both exist, the one that exists, or 0; a difference exists when both pixels are inside the image and
+ *   neither is a miss pixel.
+ * Pass k = 0 .. iterations - 1 with step s = 2^k, over the taps q = p + s (i, j), i, j in -2 .. 2 (j outer, i inner),
+ * taps outside the image skipped, h = [1 4 6 4 1] / 16:
+ *   d_c = mean over channels of (c_p - c_q)^2 / (sigma_color^2 v_p + color_eps)
+ *   d_n = |n_p - n_q|^2 / sigma_normal^2
+ *   d_z = 0 for two miss pixels; the tap is skipped when exactly one is a miss pixel; 0 when z_p == z_q; otherwise
+ *         |z_p - z_q| / (sigma_depth |gx s i + gy s j| + depth_eps |z_p|)
+ *   w = h_i h_j exp(-(d_c + d_n + d_z));   c'_p = sum w c_q / sum w;   v'_p = sum w^2 v_q / (sum w)^2
+ * A tap whose c_q or v_q is not finite is skipped; a pixel whose c_p or v_p is not finite has d_c = 0 for every tap
+ * (it is rebuilt from its neighbours); with no tap left c' = v' = 0. The last pass writes c' a to rgb_out.
+ *
+ * on_device = 1: the four pointers are device pointers aligned to 16 bytes and the call is ordered on `stream` like
+ * rt_trace_rays; 0: host pointers, the call returns when rgb_out is filled. The launches stay on the caller's stream.
+ * Whole images only (a filter needs its neighbours): with several GPUs, denoise the gathered frame. The scratch,
+ * 14 T a pixel, belongs to the context, grows on demand and is no part of the partial-sum budget.
+ * Adds iterations + 1 to rt_counters.launches and nothing else. */
+#define RT_DENOISE_DEMODULATE 1
+typedef struct rt_denoise_params {
+  int32_t width, height, iterations, precision, on_device, flags;
+  double sigma_color, sigma_normal, sigma_depth, albedo_eps, color_eps, depth_eps;
+} rt_denoise_params; /* 72 bytes, no padding */
+/* The parameter rules alone, on the host (no device): sides in [1, 65535] with width * height < 2^31, iterations in
+ * [1, 8], a known precision, flags within RT_DENOISE_DEMODULATE, the sigmas finite and > 0, the eps finite and >= 0,
+ * albedo_eps > 0 when demodulating. RT_OK, or RT_ERR_INVALID_ARGUMENT with the reason in why (n bytes). */
+rt_status rt_denoise_check(const rt_denoise_params* params, char* why, size_t n);
+/* RT_ERR_INVALID_ARGUMENT: a null pointer (var excepted), parameters rt_denoise_check refuses, device pointers not
+ * aligned to 16 bytes. On an error nothing is launched and nothing is written. */
+rt_status rt_denoise(rt_context* ctx, const rt_denoise_params* params, const void* rgb_in, const double* feat,
+                     const double* var, void* rgb_out, void* stream);
 
 /* ---- multi-GPU driver: the framebuffer tiled over the devices of one node ----
  *
