@@ -16,7 +16,7 @@ HIPFLAGS ?= -O3 -std=c++17 -fPIC -Wall -ffp-contract=on -fno-slp-vectorize --off
 LIB_SRCS := $(PKG)/csrc/rt_kernels.hip $(PKG)/csrc/rt_render.hip $(PKG)/csrc/rt_multi.hip $(PKG)/csrc/scene_compile.cpp
 # (csrc/rt_denoise.hip, the denoiser's kernels, is compiled as part of rt_render.hip, which includes it: the library
 # stays the four translation units its development variants and tests/test_dev_only.py build)
-LIB_HDRS := $(PKG)/csrc/rt_device.h $(PKG)/csrc/rt_room.h $(PKG)/csrc/rt_types.h $(PKG)/csrc/rt_launch.h $(PKG)/csrc/rt_plan.h $(PKG)/csrc/rt_denoise.h $(PKG)/csrc/rt_denoise.hip $(PKG)/csrc/rt_sin.h $(PKG)/csrc/rt_scene.h $(PKG)/csrc/scene_compile.h include/rt_hip.h
+LIB_HDRS := $(PKG)/csrc/rt_device.h $(PKG)/csrc/rt_room.h $(PKG)/csrc/rt_types.h $(PKG)/csrc/rt_launch.h $(PKG)/csrc/rt_context.h $(PKG)/csrc/rt_plan.h $(PKG)/csrc/rt_denoise.h $(PKG)/csrc/rt_denoise.hip $(PKG)/csrc/rt_sin.h $(PKG)/csrc/rt_scene.h $(PKG)/csrc/scene_compile.h include/rt_hip.h
 
 CXX      ?= g++
 CXXFLAGS ?= -O2 -std=c++17 -fPIC -Wall -Wextra -Wno-unused-parameter

@@ -482,20 +482,27 @@ inline const char* adaptive_params_error(const rt_adaptive_params& p) {
 // become resident as launch n's retire. k_persist never waits for another kernel, so two resident launches cannot
 // deadlock. The resolves, and so everything the caller sees, stay on the caller's stream.
 //
-// The one home of the ordering: for the context's next persistent launch, which lane and buffer set it takes and
-// what it waits for (rt_render.hip turns the answer into events; tests/test_lane_plan.py).
-struct LaneQuery {
+// The one home of the ordering: what a context remembers between the launches of its lanes (LaneState), for its next
+// persistent launch which lane and buffer set it takes and what it waits for (lane_plan), and what the launch leaves
+// behind for the one after it (lane_advance). rt_render.hip's one_pass() turns a plan into events and launches;
+// tests/test_lane_plan.py drives the three through tests/native/lane_plan_dump.cpp.
+struct LaneState {
+  uint64_t n = 0;               // launches that went through the lanes on this context so far
+  bool inputs_written = false;  // something the kernel reads (scene, camera view, pixel map) was queued on a caller's
+                                // stream after the last lane launch that waited for that stream
+  bool prev_overlapped = false;  // the context's last path launch went through the lanes
+  bool lane_stale[2] = {false, false};  // the lane has not waited for the inputs event since it was last recorded
+};
+// The question of one launch: the context's state as it stands before the launch (the base, so q.n, q.inputs_written,
+// q.prev_overlapped and q.lane_stale are the state's own fields, defined once) and what is known of the call.
+struct LaneQuery : LaneState {
+  void set_state(const LaneState& s) { static_cast<LaneState&>(*this) = s; }
   bool knob;             // RT_FRAME_OVERLAP (default on)
   bool device_out;       // a device-output render: the call returns before the image is there
   bool persist;          // the persistent schedule (the wavefront schedule syncs with the host between launches)
   bool shared_scratch;   // the launch writes the context's wide spill area, which is indexed by lane alone
   bool second_set;       // the second lane and buffer set exist (false: their allocation failed)
-  uint64_t n;            // launches that went through the lanes on this context so far
-  bool inputs_written;   // something the kernel reads (scene, camera view, pixel map) was queued on a caller's
-                         // stream after the last lane launch that waited for that stream
-  bool prev_overlapped;  // the context's last path launch went through the lanes
-  bool lane_stale[2];    // the lane has not waited for the inputs event since it was last recorded
-  bool pending;         // the context has work outstanding on `prev`
+  bool pending;          // the context has work outstanding on `prev`
   const void* caller;    // the stream of this call
   const void* prev;      // the stream of the outstanding work
 };
@@ -526,6 +533,21 @@ inline LanePlan lane_plan(const LaneQuery& q) {
   pl.record_inputs = q.inputs_written || !q.prev_overlapped;
   pl.wait_inputs = pl.record_inputs || q.lane_stale[pl.lane];
   return pl;
+}
+// The state after the launch `pl` plans.
+inline void lane_advance(LaneState& s, const LanePlan& pl) {
+  if (!pl.overlap) {
+    s.prev_overlapped = false;
+    s.inputs_written = false;  // the launch runs on the stream the inputs were queued on
+    return;
+  }
+  if (pl.record_inputs) {
+    s.inputs_written = false;
+    s.lane_stale[0] = s.lane_stale[1] = true;  // neither lane is behind this event yet
+  }
+  if (pl.wait_inputs) s.lane_stale[pl.lane] = false;
+  s.prev_overlapped = true;
+  s.n++;
 }
 
 }  // namespace rtd

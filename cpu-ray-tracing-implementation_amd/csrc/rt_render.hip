@@ -1,8 +1,15 @@
-// rt_render.hip -- the host side of librt_hip.so: contexts and their device buffers, render<R>() and its two
-// schedules (over a camera's tiles, or over a ray batch: rt_radiance, or over a pixel list: a round of
-// render_adaptive<R>(), the round loop of rt_render_adaptive), the query path (trace_rays<R>(), occluded<R>(),
-// camera_rays(), render_aov<R>()), and the C ABI of include/rt_hip.h with its argument checks. It contains no kernel: what a render launches goes through
-// rt_launch.h (rt_kernels.hip), and its item layout and kernel family come from rt_plan.h.
+// rt_render.hip -- the host side of librt_hip.so, in the order of the file:
+//  - (rt_context.h: contexts and their device buffers -- rt_context, DevBuf, ensure, wait_pending, settle;)
+//  - the two schedules of a path launch (run_persistent, run_wavefront);
+//  - render<R>(): the path-traced pixels of one PixelSource -- a camera's tiles (rt_render_tiles), a ray batch
+//    (rt_radiance) or a camera's pixel list (a round of rt_render_adaptive) -- as a list of named steps, of which
+//    one_pass() is the only one that launches a path kernel;
+//  - the query path (trace_rays<R>(), occluded<R>(), camera_rays(), render_aov<R>()), the round loop of
+//    rt_render_adaptive (render_adaptive<R>()) and denoise<T>();
+//  - the C ABI of include/rt_hip.h with its argument checks.
+// It contains no kernel of its own: what a render launches goes through rt_launch.h (rt_kernels.hip), and its item
+// layout, kernel family and lane ordering come from rt_plan.h. (The denoiser's kernels, rt_denoise.hip, are included at
+// the end, so that the library stays four translation units.)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -17,77 +24,12 @@
 #include <vector>
 
 #include "../../include/rt_hip.h"
+#include "rt_context.h"
 #include "rt_launch.h"
 #include "rt_plan.h"
 #include "scene_compile.h"
 
 using namespace rtd;
-
-struct DevBuf {
-  void* ptr = nullptr;
-  size_t bytes = 0;
-};
-
-struct rt_context {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  std::string err;
-  CompiledScene scene;
-  bool has_scene = false;
-  DevBuf scene32, scene64;
-  DevBuf state, partial, pixmap, queue0, queue1, blk, out_tmp, counters, camx, heads, tiles;
-  DevBuf wide_spill;  // the wide traversal's stack entries past wide_lds_stack (deep trees in HBM)
-  CamDev cam_host;  // source of camx (kept alive for the async copy)
-  uint32_t* total_host = nullptr;  // pinned: [0] live slots, [1] fault word, [16..] segment counter shards
-  uint64_t samples = 0;
-  rt_counters last{};  // host-known totals since rt_reset_counters; segments and step_ms settle in settle()
-  int timing = 0;
-  std::vector<hipEvent_t> events;
-  // asynchronous renders (device output): what rt_stats / rt_reset_counters / a host-output render
-  // settle with one sync -- the stream, the timing events recorded since the last settle
-  hipStream_t pend_stream = nullptr;
-  bool pending = false;
-  size_t ev_used = 0;
-  DevBuf fault;  // sticky internal-error word of the persistent kernel (zeroed by rt_reset_counters)
-  // inputs kept on the device while they do not change between calls
-  std::vector<uint4> tiles_dev;  // the tile list k_pixmap last expanded into pixmap
-  void* pixmap_for = nullptr;    // pixmap buffer that expansion went to
-  uint32_t pixmap_npix = 0;      // pixels it expanded: a tile entry {x0, y0, width, first} does not
-                                 // hold the height, so the last tile can change with the list equal
-  CamDev cam_dev{};              // the camera view in camx
-  bool cam_valid = false;
-  // the compiled scene is copied into scene32 / scene64 by the first render after rt_scene_upload,
-  // on that render's stream: a copy made on another stream is not guaranteed visible to the kernels
-  // of the render stream (their launch need not invalidate the L2 lines of the previous scene)
-  bool scene_dirty32 = false, scene_dirty64 = false;
-  // ray queries (rt_trace_rays): the compiled scene's (object, material) tables, copied like the scene by the first
-  // query after rt_scene_upload on that query's stream; device copies of a host-pointer query's rays and outputs
-  DevBuf ids, q_rays, q_geom, q_ids;
-  bool ids_dirty = false;
-  // the launch lanes (rt_plan.h lane_plan): lane 0 is `stream`, lane 1 a second internal stream; launch n of the
-  // lanes runs on lane n & 1 and writes partial / heads (n even) or partial2 / heads2 (n odd). Made by the first
-  // render that overlaps; a context that never does holds none of it.
-  hipStream_t lane1 = nullptr;
-  DevBuf partial2, heads2;
-  hipEvent_t ev_done[2] = {nullptr, nullptr};     // launch on this lane finished (the caller's stream waits for it)
-  hipEvent_t ev_resolved[2] = {nullptr, nullptr}; // this set's resolve finished, on the caller's stream
-  hipEvent_t ev_inputs = nullptr;                 // the caller's stream, behind the inputs a call queued there
-  bool lanes_failed = false;     // making them failed once (out of memory): the context stays serial
-  uint64_t lane_launches = 0;    // launches that went through the lanes
-  bool lanes_live = false;       // a lane may still be running (cleared by wait_pending)
-  bool inputs_written = false;   // LaneQuery::inputs_written
-  bool prev_overlapped = false;  // LaneQuery::prev_overlapped
-  bool lane_stale[2] = {false, false};  // LaneQuery::lane_stale
-  uint64_t max_lanes = 0;        // the most lanes the device can hold, 2,048 a CU (auto_run's bound); 0: not asked yet
-  std::vector<uint8_t> ev_lane;  // per pair of timing events: recorded on a lane (settle() clamps its start)
-  // adaptive sampling (rt_render_adaptive): the pixels' moment records, the two pixel lists the rounds alternate
-  // between (positions, and the pixels' slots in the outputs and records), the select's block counts, and device
-  // copies of a host-pointer call's out_spp and out_err (out_rgb's is out_tmp)
-  DevBuf ad_acc, ad_pix[2], ad_slot[2], ad_blk, ad_spp, ad_err;
-  // denoising (rt_denoise): the working records, kDnScratchT T a pixel; a host-pointer call's inputs and output are
-  // staged in out_tmp (rgb, in and out), q_rays (feat) and q_geom (var)
-  DevBuf dn_scratch;
-};
 
 namespace {
 
@@ -121,111 +63,9 @@ CamDev make_view(const rt_camera_desc* c) {
   return v;
 }
 
-std::mutex g_err_mu;
-std::string g_create_err;
-
-rt_status set_err(rt_context* c, rt_status s, const std::string& m) {
-  if (c) {
-    c->err = m;
-  } else {
-    std::lock_guard<std::mutex> lk(g_err_mu);
-    g_create_err = m;
-  }
-  return s;
-}
-
-#define RT_HIP(ctx, call)                                                                   \
-  do {                                                                                      \
-    hipError_t e_ = (call);                                                                 \
-    if (e_ != hipSuccess)                                                                   \
-      return set_err((ctx), RT_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
-  } while (0)
-
-// Wait on the host for everything of this context that may still run. pend_stream alone covers the lanes in the
-// normal course (it waits for every lane launch before that launch's resolve); the lanes are waited for too, so
-// that a call which failed between a launch and that wait leaves nothing behind either. `pending` stays: the
-// device-side results are still to be folded in by settle().
-rt_status wait_pending(rt_context* c) {
-  if (c->pending) RT_HIP(c, hipStreamSynchronize(c->pend_stream));
-  if (c->lanes_live) {
-    RT_HIP(c, hipStreamSynchronize(c->stream));
-    if (c->lane1) RT_HIP(c, hipStreamSynchronize(c->lane1));
-    c->lanes_live = false;
-  }
-  return RT_OK;
-}
-
-// Grow a context buffer. The only work that can still read the old buffer is this context's
-// outstanding device-output render (host-output renders return finished, and a render on another
-// stream waits for pend_stream first): wait for that stream and the lanes, not for the whole device.
-rt_status ensure(rt_context* c, DevBuf& b, size_t bytes) {
-  if (b.ptr && b.bytes >= bytes) return RT_OK;
-  if (b.ptr) {
-    rt_status w;
-    if ((w = wait_pending(c)) != RT_OK) return w;
-    RT_HIP(c, hipFree(b.ptr));
-    b.ptr = nullptr;
-    b.bytes = 0;
-  }
-  size_t want = std::max<size_t>(bytes, 256);
-  hipError_t e = hipMalloc(&b.ptr, want);
-  if (e != hipSuccess) {
-    b.ptr = nullptr;
-    (void)hipGetLastError();
-    return set_err(c, RT_ERR_OUT_OF_MEMORY,
-                   "hipMalloc(" + std::to_string(want) + " bytes): " + hipGetErrorString(e));
-  }
-  b.bytes = want;
-  return RT_OK;
-}
-
-hipEvent_t take_event(rt_context* c, size_t idx) {
-  while (c->events.size() <= idx) {
-    hipEvent_t e = nullptr;
-    if (hipEventCreate(&e) != hipSuccess) return nullptr;
-    c->events.push_back(e);
-  }
-  return c->events[idx];
-}
-
-// Wait for the context's outstanding renders and fold their device-side results into c->last:
-// the cumulative segment count, the kernel time of the timing events, the fault word.
-rt_status settle(rt_context* c) {
-  if (!c->pending) return RT_OK;
-  {
-    rt_status w;
-    if ((w = wait_pending(c)) != RT_OK) return w;
-  }
-  c->pending = false;
-  unsigned long long* shards = (unsigned long long*)(c->total_host + 16);
-  RT_HIP(c, hipMemcpy(shards, c->counters.ptr, sizeof(unsigned long long) * kSegShards, hipMemcpyDeviceToHost));
-  uint64_t segs = 0;
-  for (int k = 0; k < kSegShards; k++) segs += shards[k];
-  c->last.segments = segs;
-  double ms = 0;
-  for (size_t k = 0; k + 1 < c->ev_used; k += 2) {
-    float a = 0;
-    RT_HIP(c, hipEventElapsedTime(&a, c->events[k], c->events[k + 1]));
-    // A lane launch's start event fires when its lane reaches it, which with two lanes is while the launch before
-    // still fills the chip. Its time counts from the later of its own start and that launch's end, so step_ms never
-    // counts a moment twice: it stays below the wall time and in steady state is the frame period (rt_counters).
-    if (k >= 2 && k / 2 < c->ev_lane.size() && c->ev_lane[k / 2]) {
-      float lead = 0;  // own start -> previous end; positive: the previous launch was still running
-      if (hipEventElapsedTime(&lead, c->events[k], c->events[k - 1]) == hipSuccess && lead > 0)
-        a = std::max(0.0f, a - lead);
-      else
-        (void)hipGetLastError();
-    }
-    ms += a;
-  }
-  c->ev_used = 0;
-  c->ev_lane.clear();
-  c->last.step_ms += ms;
-  uint32_t fault = 0;
-  if (c->fault.ptr) RT_HIP(c, hipMemcpy(&fault, c->fault.ptr, 4, hipMemcpyDeviceToHost));
-  if (fault) return set_err(c, RT_ERR_HIP, "a path did not finish (internal error)");
-  return RT_OK;
-}
+// What a build without the kernels of a family (RT_DEV_ONLY) says when it refuses a scene or a call
+std::string dev_only_lacks(const std::string& what) { return "this build (RT_DEV_ONLY) has no " + what; }
+std::string dev_only_lacks(KernelFamily fam) { return dev_only_lacks(std::string(family_name(fam)) + " kernels"); }
 
 template <class R>
 DevScene<R> dev_scene(const SceneHeader& h, void* base) {
@@ -279,9 +119,7 @@ rt_status wide_spill_area(rt_context* c, const SceneHeader& hdr, DevScene<R>& sc
   const uint32_t wide_need = hdr.wide_stack;
   constexpr uint32_t kWideLdsStack = wide_lds_stack<R>();
   if (hdr.has_wide && wide_need > kWideLdsStack) {
-    int ncu = 0;
-    RT_HIP(c, hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->device));
-    const uint32_t lanes = (uint32_t)std::max(ncu, 1) * 2048u;  // 32 waves of 64 per CU at most
+    const uint32_t lanes = device_max_lanes(c);
     rt_status s;
     if ((s = ensure(c, c->wide_spill, 4ull * (wide_need - kWideLdsStack) * lanes)) != RT_OK) return s;
     sc.wide_spill = (uint32_t*)c->wide_spill.ptr;
@@ -436,7 +274,7 @@ rt_status pixel_map(rt_context* c, const std::vector<uint4>& tl, uint32_t npix, 
     c->tiles_dev = tl;  // the copy's source outlives this call
     c->pixmap_for = c->pixmap.ptr;
     c->pixmap_npix = npix;
-    c->inputs_written = true;  // (whoever queues it: a feature-buffer call's map is a later render's input too)
+    c->lane_state.inputs_written = true;  // (whoever queues it: a feature-buffer call's map is a later render's input too)
     RT_HIP(c, hipMemcpyAsync(c->tiles.ptr, c->tiles_dev.data(), sizeof(uint4) * tl.size(), hipMemcpyHostToDevice, st));
     launch_pixmap((const uint4*)c->tiles.ptr, (uint32_t)tl.size(), npix, (uint32_t*)c->pixmap.ptr, st);
   }
@@ -449,8 +287,8 @@ rt_status camera_view(rt_context* c, const rt_camera_desc* cam, hipStream_t st) 
   c->cam_host = make_view(cam);
   if ((s = ensure(c, c->camx, sizeof(CamDev))) != RT_OK) return s;
   if (!c->cam_valid || std::memcmp(&c->cam_dev, &c->cam_host, sizeof(CamDev)) != 0) {
-    c->inputs_written = true;
-    RT_HIP(c, hipMemcpyAsync(c->camx.ptr, &c->cam_host, sizeof(CamDev), hipMemcpyHostToDevice, st));
+    c->lane_state.inputs_written = true;
+    RT_HIP(c, hipMemcpyAsync(c->camx.ptr,&c->cam_host, sizeof(CamDev), hipMemcpyHostToDevice, st));
     c->cam_dev = c->cam_host;
     c->cam_valid = true;
   }
@@ -505,13 +343,12 @@ rt_status scene_to_device(rt_context* c, bool f64, hipStream_t st, LaneQuery* lq
   if (dirty) {
     const std::vector<unsigned char>& blob = f64 ? c->scene.blob64 : c->scene.blob32;
     void* sbase = f64 ? c->scene64.ptr : c->scene32.ptr;
-    c->inputs_written = true;
+    c->lane_state.inputs_written = true;
     RT_HIP(c, hipMemcpyAsync(sbase, blob.data(), blob.size(), hipMemcpyHostToDevice, st));
     dirty = false;
     // outstanding from here on, whatever the call does next (an empty tile list or max_depth <= 0
     // launches nothing that reads the scene): a later call on another stream waits for st
-    c->pending = true;
-    c->pend_stream = st;
+    mark_pending(c, st);
   }
   return RT_OK;
 }
@@ -538,116 +375,83 @@ struct PixelList {
   AdaptiveAcc* acc;
 };
 
-// cam and tiles, or (cam = tiles = nullptr) the ray batch rb, or cam and (tiles = out = nullptr, out_dev = 1) the
-// pixel list pl
-template <class R>
-rt_status render(rt_context* c, const rt_camera_desc* cam, const rt_render_params* prm, const rt_tile* tiles,
-                 int32_t ntiles, void* out, int32_t out_dev, hipStream_t st, const RayBatch* rb = nullptr,
-                 const PixelList* pl = nullptr) {
-  const bool f64 = sizeof(R) == 8;
-  const CompiledScene& cs = c->scene;
-  const SceneHeader& hdr = f64 ? cs.hdr64 : cs.hdr;
-  void* sbase = f64 ? c->scene64.ptr : c->scene32.ptr;
-  auto t0 = std::chrono::steady_clock::now();
-  rt_status s;
-  LaneQuery lq{};  // (the rest of the query is filled in below)
-  if ((s = scene_to_device(c, f64, st, &lq)) != RT_OK) return s;
+// The pixels of one render<R>() call and where their result goes. Three kinds of source:
+//  - SRC_TILES: `ntiles` tiles of the image of `cam`; the result is the tiles' packed image;
+//  - SRC_RAYS: the ray batch `rays`, ray i the call's pixel i; the result is one value a ray;
+//  - SRC_LIST: the pixel list `list` of the image of `cam`; no image, every pass goes into the records at list.acc.
+// The result is written to `out`: device memory when out_dev, and the call returns with its work queued, else host
+// memory, and the call returns finished. A list has no `out` and is a device-output call.
+// Every rule of render<R>() that depends on the kind is a member here, written once; render<R>() and its steps ask
+// the source and never its kind.
+enum SourceKind { SRC_TILES, SRC_RAYS, SRC_LIST };
+struct PixelSource {
+  SourceKind kind;
+  const rt_camera_desc* cam;  // SRC_TILES, SRC_LIST
+  const rt_tile* tiles;       // SRC_TILES
+  int32_t ntiles;
+  RayBatch rays;              // SRC_RAYS
+  PixelList list;             // SRC_LIST
+  void* out;
+  bool out_dev;
 
-  // pixel map: tiles packed in order, row-major inside each tile (expanded by k_pixmap)
-  uint64_t npix64 = rb ? rb->n : pl ? pl->n : 0;
-  const std::vector<uint4> tl = (rb || pl) ? std::vector<uint4>() : pack_tiles(tiles, ntiles, npix64);
-  if (npix64 >= (1ull << 31)) return set_err(c, RT_ERR_INVALID_ARGUMENT, "too many pixels in one call");
-  const uint32_t npix = (uint32_t)npix64;
-  if (npix == 0) return RT_OK;
-  const size_t out_elems = 3ull * npix;
-  void* dout = out;
-  if (!out_dev) {
-    if ((s = ensure(c, c->out_tmp, out_elems * sizeof(R))) != RT_OK) return s;
-    dout = c->out_tmp.ptr;
+  static PixelSource of_tiles(const rt_camera_desc* cam, const rt_tile* tiles, int32_t ntiles, void* out, bool out_dev) {
+    PixelSource s{};
+    s.kind = SRC_TILES, s.cam = cam, s.tiles = tiles, s.ntiles = ntiles, s.out = out, s.out_dev = out_dev;
+    return s;
+  }
+  static PixelSource of_rays(const RayBatch& rb, void* out, bool out_dev) {
+    PixelSource s{};
+    s.kind = SRC_RAYS, s.rays = rb, s.out = out, s.out_dev = out_dev;
+    return s;
+  }
+  static PixelSource of_list(const rt_camera_desc* cam, const PixelList& pl) {
+    PixelSource s{};
+    s.kind = SRC_LIST, s.cam = cam, s.list = pl, s.out = nullptr, s.out_dev = true;
+    return s;
   }
 
-  if (prm->max_depth <= 0 && pl) {  // ... so the batches' sums are zero: the records count them and stay as they are
-    launch_resolve_moments<R>(nullptr, pl->slots, npix, (uint32_t)(prm->spp / prm->samples_per_item), pl->acc, st);
-    c->last.launches++;
-    RT_HIP(c, hipGetLastError());
-    c->pending = true;
-    c->pend_stream = st;
-    c->last.samples += (uint64_t)npix * (uint32_t)prm->spp;
-  } else if (prm->max_depth <= 0) {  // ray_color(r, 0) is black for every sample (camera.h:194-195)
-    launch_zero<R>((R*)dout, (uint64_t)out_elems, st);
-  } else {
-    const uint32_t spp = (uint32_t)prm->spp;
-    // the default schedule is persistent (k_persist); an explicit segments_per_launch selects the
-    // launch-per-K-segments wavefront with HBM path state and live-slot compaction
-    const bool persist = prm->segments_per_launch <= 0;
-    const bool ordered = prm->traversal == RT_TRAV_ORDERED;
-    const PathKernel kind = rb ? radiance_kernel(hdr, sizeof(typename WWord<R>::T), ordered, cs.stack_need)
-                               : path_kernel(hdr, sizeof(typename WWord<R>::T), cam->mode, persist, ordered, cs.stack_need);
-    if (!family_built(kind.fam))
-      return set_err(c, RT_ERR_UNSUPPORTED,
-                     std::string("this build (RT_DEV_ONLY) has no ") + family_name(kind.fam) + " kernels");
-    // the item layout and the passes (the full image's pixels decide the item size, not this call's tiles)
-    // (a batch is its own full image: with samples_per_item given, the layout depends on spp alone)
-    const ItemPlan plan = plan_items(spp, prm->samples_per_item, kind.fam == KF_FLAT,
-                                     rb ? (uint64_t)npix : (uint64_t)cam->image_width * (uint64_t)cam->image_height, npix,
-                                     sizeof(R), env_knobs());
-    const uint32_t n_items = npix * plan.cpp;  // items of the largest pass
-    uint32_t P = prm->pool_slots > 0 ? (uint32_t)prm->pool_slots
-                 : persist       ? kAutoPersistLanes
-                                 : (f64 ? kAutoPool64 : kAutoPool32);
-    P = std::max<uint32_t>(1, std::min(P, n_items));
-    const uint32_t nblk_max = (P + kBlock - 1) / kBlock;
+  // The call's pixels: their count and, for tiles, the packed list that expand_map() takes (else empty)
+  std::vector<uint4> packed_tiles(uint64_t& npix) const {
+    if (kind == SRC_TILES) return pack_tiles(tiles, ntiles, npix);
+    npix = kind == SRC_RAYS ? rays.n : list.n;
+    return {};
+  }
+  // The pixel map: tiles packed in order, row-major inside each tile (expanded by k_pixmap into c->pixmap); a list is
+  // its own map as it stands, and a batch has none (the kernel reads ray i where it would read pixel i of the map)
+  rt_status expand_map(rt_context* c, const std::vector<uint4>& tl, uint32_t npix, hipStream_t st) const {
+    return kind == SRC_TILES ? pixel_map(c, tl, npix, st) : RT_OK;
+  }
+  const uint32_t* pixmap(const rt_context* c) const {
+    return kind == SRC_LIST ? list.pixmap : (const uint32_t*)c->pixmap.ptr;
+  }
+  // What decides the item size (plan_items): the full image's pixels, not this call's tiles. A batch is its own full
+  // image: with samples_per_item given, the layout depends on spp alone.
+  uint64_t image_pixels(uint32_t npix) const {
+    return kind == SRC_RAYS ? (uint64_t)npix : (uint64_t)cam->image_width * (uint64_t)cam->image_height;
+  }
+  PathKernel kernel(const CompiledScene& cs, const SceneHeader& hdr, size_t word_bytes, bool persist, bool ordered) const {
+    return kind == SRC_RAYS ? radiance_kernel(hdr, word_bytes, ordered, cs.stack_need)
+                            : path_kernel(hdr, word_bytes, cam->mode, persist, ordered, cs.stack_need);
+  }
+  // Whether the call's launches may go through the launch lanes (LaneQuery::knob, with RT_FRAME_OVERLAP).
+  // A ray batch stays on the caller's stream: its rays are the caller's, written on that stream, and a lane would
+  // have to wait for them before every launch -- there is no unchanged-input case for the lanes to overlap.
+  // A pixel list stays there too: the list is written on that stream just before, and the host waits between rounds.
+  bool may_use_lanes() const { return kind == SRC_TILES; }
 
-    // path state: 5 R4 arrays (O, D, T, L, A) + uint4 keys (S) + uint4 exclusion/pixel (X), each P long
-    auto al = [](size_t x) { return (x + 255) & ~size_t(255); };
-    const size_t r4 = al(sizeof(R4<R>) * (size_t)P), sb = al(16 * (size_t)P), xb = al(16 * (size_t)P);
-    if (!persist) {
-      if ((s = ensure(c, c->state, 5 * r4 + sb + xb)) != RT_OK) return s;
-      if ((s = ensure(c, c->queue0, 4ull * P)) != RT_OK) return s;
-      if ((s = ensure(c, c->queue1, 4ull * P)) != RT_OK) return s;
-    }
-    if ((s = ensure(c, c->partial, plan.partial_bytes)) != RT_OK) return s;
-    c->last.passes += plan.passes;
-    c->last.partial_bytes = plan.partial_bytes;
-    if ((s = ensure(c, c->blk, 4ull * (nblk_max + 2))) != RT_OK) return s;
-    if (!rb && !pl && (s = pixel_map(c, tl, npix, st)) != RT_OK) return s;
-
-    unsigned char* sp = (unsigned char*)c->state.ptr;
-    LaunchParams<R> p{};
-    p.sc = dev_scene<R>(hdr, sbase);
-    if ((s = wide_spill_area<R>(c, hdr, p.sc)) != RT_OK) return s;
-    if (prm->traversal == RT_TRAV_ORDERED) p.sc.has_flat = p.sc.has_wide = 0;
-    p.sc.cam64 = nullptr;  // set with the camera below (perspective only)
-    p.O = (R4<R>*)sp;
-    p.D = (R4<R>*)(sp + r4);
-    p.T = (R4<R>*)(sp + 2 * r4);
-    p.L = (R4<R>*)(sp + 3 * r4);
-    p.A = (R4<R>*)(sp + 4 * r4);
-    p.S = (uint4*)(sp + 5 * r4);
-    p.X = (uint4*)(sp + 5 * r4 + sb);
-    p.partial = (R*)c->partial.ptr;
-    p.pixmap = pl ? pl->pixmap : (const uint32_t*)c->pixmap.ptr;
-    p.queue = nullptr;
-    p.n = P;
-    p.P = P;
-    p.npix = npix;
-    div_magic(npix, p.npix_m, p.npix_k);
-    p.n_items = n_items;
-    p.chunk = plan.chunk;
-    p.k_bulk = plan.k_bulk;
-    p.tail_chunk = plan.tail_chunk;
-    p.spp = spp;
-    p.first_sample = (uint32_t)std::max(0, prm->first_sample);
-    p.max_depth = prm->max_depth;
-    p.seed = prm->seed;
-    if (rb) {  // no camera: cam64 stays null, so a near-edge quad re-decision (quad_edge64) takes the given ray, as a query's
-      p.rays = rb->rays;
-      p.ray_base = rb->ray_base;
+  // The source's part of the launch parameters: the camera's view, or the batch's rays (staged in q_rays unless
+  // they are on the device), queued on `st`
+  template <class R>
+  rt_status fill(rt_context* c, LaunchParams<R>& p, uint32_t npix, hipStream_t st) const {
+    rt_status s;
+    if (kind == SRC_RAYS) {  // no camera: cam64 stays null, so a near-edge quad re-decision (quad_edge64) takes the given ray, as a query's
+      p.rays = rays.rays;
+      p.ray_base = rays.ray_base;
       p.cam_mode = RT_CAM_PERSPECTIVE;
-      if (!rb->on_device) {
+      if (!rays.on_device) {
         if ((s = ensure(c, c->q_rays, 64ull * npix)) != RT_OK) return s;
         p.rays = (const double*)c->q_rays.ptr;
-        RT_HIP(c, hipMemcpyAsync(c->q_rays.ptr, rb->rays, 64ull * npix, hipMemcpyHostToDevice, st));
+        RT_HIP(c, hipMemcpyAsync(c->q_rays.ptr, rays.rays, 64ull * npix, hipMemcpyHostToDevice, st));
       }
     } else {
       p.W = (uint32_t)cam->image_width;
@@ -656,110 +460,272 @@ rt_status render(rt_context* c, const rt_camera_desc* cam, const rt_render_param
       p.camx = (const CamDev*)c->camx.ptr;
       if (p.cam_mode == RT_CAM_PERSPECTIVE) p.sc.cam64 = p.camx;
     }
-    p.seg_shards = (unsigned long long*)c->counters.ptr;
-    p.K = prm->segments_per_launch > 0 ? std::min(prm->segments_per_launch, 64) : kAutoSegments;
-    if (c->timing && c->ev_used > 4096 && (s = settle(c)) != RT_OK) return s;  // bound the pending events
-    if (persist) {
-      if ((s = ensure(c, c->fault, 4)) != RT_OK) return s;
-      p.persist = kPersist;
-      p.fault = (uint32_t*)c->fault.ptr;
-      if ((s = ensure(c, c->heads, 4ull * kHeads * kHeadStride)) != RT_OK) return s;
+    return RT_OK;
+  }
+  // The resolve of the pass of chunks [c0, c0 + pc) of plan.nchunks, on `st`: into the image at `dout`, or a list's
+  // into its records' moments
+  template <class R>
+  void resolve(const R* partial, uint32_t npix, uint32_t c0, uint32_t pc, const ItemPlan& plan, uint32_t spp, void* dout,
+               hipStream_t st) const {
+    if (kind == SRC_LIST)
+      launch_resolve_moments<R>(partial, list.slots, npix, pc, list.acc, st);
+    else
+      launch_resolve<R>(partial, npix, pc, spp, (R*)dout, c0 == 0, c0 + pc >= plan.nchunks, st);
+  }
+  // max_depth <= 0: ray_color(r, 0) is black for every sample (camera.h:194-195), so the image is zero; a list's
+  // batches' sums are zero: the records count them and stay as they are
+  template <class R>
+  rt_status depth0(rt_context* c, const rt_render_params* prm, uint32_t npix, void* dout, hipStream_t st) const {
+    if (kind != SRC_LIST) {
+      launch_zero<R>((R*)dout, 3ull * npix, st);
+      return RT_OK;
+    }
+    launch_resolve_moments<R>(nullptr, list.slots, npix, (uint32_t)(prm->spp / prm->samples_per_item), list.acc, st);
+    c->last.launches++;
+    RT_HIP(c, hipGetLastError());
+    mark_pending(c, st);
+    c->last.samples += (uint64_t)npix * (uint32_t)prm->spp;
+    return RT_OK;
+  }
+};
+
+// One render<R>() call, as its steps build it up (each step's comment says what it adds)
+template <class R>
+struct RenderCall {
+  const PixelSource& src;
+  const rt_render_params* prm;
+  hipStream_t st;
+  uint32_t npix = 0;
+  void* dout = nullptr;  // the result on the device: src.out, or out_tmp behind a host `out`
+  // plan_call
+  uint32_t spp = 0;
+  bool persist = true;
+  PathKernel kind{};
+  ItemPlan plan{};
+  uint32_t P = 0, nblk_max = 0;
+  // path_buffers
+  size_t r4 = 0, sb = 0;  // the bytes of an R4 array and of the key array of the path state
+  // fill_params
+  LaunchParams<R> p{};
+  // scene_to_device (pending, caller, prev), lane_setup (the rest)
+  LaneQuery lq{};
+  uint32_t forced_run = 0;
+};
+
+// Step: the kernel, the item layout and the pool of the call.
+template <class R>
+rt_status plan_call(rt_context* c, RenderCall<R>& rc) {
+  const rt_render_params* prm = rc.prm;
+  const CompiledScene& cs = c->scene;
+  rc.spp = (uint32_t)prm->spp;
+  // the default schedule is persistent (k_persist); an explicit segments_per_launch selects the
+  // launch-per-K-segments wavefront with HBM path state and live-slot compaction
+  rc.persist = prm->segments_per_launch <= 0;
+  rc.kind = rc.src.kernel(cs, sizeof(R) == 8 ? cs.hdr64 : cs.hdr, sizeof(typename WWord<R>::T), rc.persist,
+                          prm->traversal == RT_TRAV_ORDERED);
+  if (!family_built(rc.kind.fam)) return set_err(c, RT_ERR_UNSUPPORTED, dev_only_lacks(rc.kind.fam));
+  // the item layout and the passes
+  rc.plan = plan_items(rc.spp, prm->samples_per_item, rc.kind.fam == KF_FLAT, rc.src.image_pixels(rc.npix), rc.npix,
+                       sizeof(R), env_knobs());
+  const uint32_t n_items = rc.npix * rc.plan.cpp;  // items of the largest pass
+  uint32_t P = prm->pool_slots > 0 ? (uint32_t)prm->pool_slots
+               : rc.persist       ? kAutoPersistLanes
+                                  : (sizeof(R) == 8 ? kAutoPool64 : kAutoPool32);
+  rc.P = std::max<uint32_t>(1, std::min(P, n_items));
+  rc.nblk_max = (rc.P + kBlock - 1) / kBlock;
+  return RT_OK;
+}
+
+// Step: the buffers a path launch writes, sized by the plan. (The persistent schedule's fault word and dequeue heads
+// are ensured at the end of fill_params, behind the inputs the call queues, where they have always been.)
+template <class R>
+rt_status path_buffers(rt_context* c, RenderCall<R>& rc) {
+  rt_status s;
+  // path state: 5 R4 arrays (O, D, T, L, A) + uint4 keys (S) + uint4 exclusion/pixel (X), each P long
+  auto al = [](size_t x) { return (x + 255) & ~size_t(255); };
+  const size_t xb = al(16 * (size_t)rc.P);
+  rc.r4 = al(sizeof(R4<R>) * (size_t)rc.P);
+  rc.sb = al(16 * (size_t)rc.P);
+  if (!rc.persist) {
+    if ((s = ensure(c, c->state, 5 * rc.r4 + rc.sb + xb)) != RT_OK) return s;
+    if ((s = ensure(c, c->queue0, 4ull * rc.P)) != RT_OK) return s;
+    if ((s = ensure(c, c->queue1, 4ull * rc.P)) != RT_OK) return s;
+  }
+  if ((s = ensure(c, c->partial, rc.plan.partial_bytes)) != RT_OK) return s;
+  c->last.passes += rc.plan.passes;
+  c->last.partial_bytes = rc.plan.partial_bytes;
+  return ensure(c, c->blk, 4ull * (rc.nblk_max + 2));
+}
+
+// Step: the launch parameters, everything that is fixed for the whole call -- from the scene, the plan and the source.
+template <class R>
+rt_status fill_params(rt_context* c, RenderCall<R>& rc) {
+  const bool f64 = sizeof(R) == 8;
+  const SceneHeader& hdr = f64 ? c->scene.hdr64 : c->scene.hdr;
+  const rt_render_params* prm = rc.prm;
+  const size_t r4 = rc.r4, sb = rc.sb;
+  rt_status s;
+  unsigned char* sp = (unsigned char*)c->state.ptr;
+  LaunchParams<R>& p = rc.p;
+  p.sc = dev_scene<R>(hdr, f64 ? c->scene64.ptr : c->scene32.ptr);
+  if ((s = wide_spill_area<R>(c, hdr, p.sc)) != RT_OK) return s;
+  if (prm->traversal == RT_TRAV_ORDERED) p.sc.has_flat = p.sc.has_wide = 0;
+  p.sc.cam64 = nullptr;  // set with the camera below (perspective only)
+  p.O = (R4<R>*)sp;
+  p.D = (R4<R>*)(sp + r4);
+  p.T = (R4<R>*)(sp + 2 * r4);
+  p.L = (R4<R>*)(sp + 3 * r4);
+  p.A = (R4<R>*)(sp + 4 * r4);
+  p.S = (uint4*)(sp + 5 * r4);
+  p.X = (uint4*)(sp + 5 * r4 + sb);
+  p.partial = (R*)c->partial.ptr;
+  p.pixmap = rc.src.pixmap(c);
+  p.queue = nullptr;
+  p.n = rc.P;
+  p.P = rc.P;
+  p.npix = rc.npix;
+  div_magic(rc.npix, p.npix_m, p.npix_k);
+  p.n_items = rc.npix * rc.plan.cpp;  // items of the largest pass
+  p.chunk = rc.plan.chunk;
+  p.k_bulk = rc.plan.k_bulk;
+  p.tail_chunk = rc.plan.tail_chunk;
+  p.spp = rc.spp;
+  p.first_sample = (uint32_t)std::max(0, prm->first_sample);
+  p.max_depth = prm->max_depth;
+  p.seed = prm->seed;
+  if ((s = rc.src.template fill<R>(c, p, rc.npix, rc.st)) != RT_OK) return s;
+  p.seg_shards = (unsigned long long*)c->counters.ptr;
+  p.K = prm->segments_per_launch > 0 ? std::min(prm->segments_per_launch, 64) : kAutoSegments;
+  if (c->timing && c->ev_used > 4096 && (s = settle(c)) != RT_OK) return s;  // bound the pending events
+  if (rc.persist) {
+    if ((s = ensure(c, c->fault, 4)) != RT_OK) return s;
+    p.persist = kPersist;
+    p.fault = (uint32_t*)c->fault.ptr;
+    if ((s = ensure(c, c->heads, 4ull * kHeads * kHeadStride)) != RT_OK) return s;
+    p.heads = (uint32_t*)c->heads.ptr;
+  }
+  return RT_OK;
+}
+
+// Step: the launch lanes (rt_plan.h lane_plan) -- what of the lane query is fixed for the call, the second lane and
+// buffer set if the call would use them, and the forced run length. The plan itself is asked per launch (one_pass),
+// so the passes of a call alternate too.
+template <class R>
+void lane_setup(rt_context* c, RenderCall<R>& rc) {
+  LaneQuery& lq = rc.lq;
+  lq.knob = env_frame_overlap() && rc.src.may_use_lanes();
+  lq.device_out = rc.src.out_dev;
+  lq.persist = rc.persist;
+  lq.shared_scratch = rc.p.sc.wide_spill != nullptr;
+  lq.second_set = true;  // asked first whether the call would overlap at all; then whether the set can be had
+  lq.second_set = lane_plan(lq).overlap && lanes_ready(c, rc.plan.partial_bytes);
+  // the run length of the queue's units (rt_plan.h RunPlan) is the knob's for a kernel that takes runs, else
+  // auto_run's (one_pass, per launch), against the most lanes the device can hold (device_max_lanes)
+  rc.forced_run = kernel_takes_runs(rc.kind) ? env_item_run() : 1;
+}
+
+// Step: one pass, the chunks [c0, c0 + plan.cpp) of every pixel. The lane plan of this launch and the state it leaves
+// (lane_plan, lane_advance); then, side by side, the overlapped launch on a lane between its events and the serial
+// launch on the caller's stream; then the resolve, on the caller's stream either way.
+template <class R>
+rt_status one_pass(rt_context* c, RenderCall<R>& rc, uint32_t c0) {
+  const ItemPlan& plan = rc.plan;
+  LaunchParams<R>& p = rc.p;
+  const hipStream_t st = rc.st;
+  rt_status s;
+  const uint32_t pc = std::min(plan.cpp, plan.nchunks - c0);
+  p.chunk0 = c0;
+  p.n_items = rc.npix * pc;
+  rc.lq.set_state(c->lane_state);
+  const LanePlan lp = lane_plan(rc.lq);
+  lane_advance(c->lane_state, lp);
+  // runs only in a stream of overlapped launches, where the next launch hides this one's longer end (auto_run)
+  const uint32_t run = rc.forced_run ? rc.forced_run
+                                     : auto_run(plan, rc.kind, rc.spp, rc.npix, device_max_lanes(c),
+                                                lp.overlap && rc.lq.prev_overlapped);
+  const RunPlan rp = plan_runs(plan, rc.spp, c0, pc, rc.npix, run);
+  p.n_units = rp.n_units;
+  p.run_cfg = run_cfg_pack(rp.runs, rp.run_log2);
+  const R* partial = (const R*)c->partial.ptr;
+  if (lp.overlap) {
+    hipStream_t lane = lp.lane ? c->lane1 : c->stream;
+    if (lp.set) {
+      p.partial = (R*)c->partial2.ptr;
+      p.heads = (uint32_t*)c->heads2.ptr;
+    } else {
+      p.partial = (R*)c->partial.ptr;
       p.heads = (uint32_t*)c->heads.ptr;
     }
-    // the launch lanes (rt_plan.h lane_plan): asked per launch, so the passes of a call alternate too
-    // A ray batch stays on the caller's stream: its rays are the caller's, written on that stream, and a lane would
-    // have to wait for them before every launch -- there is no unchanged-input case for the lanes to overlap.
-    // A pixel list stays there too: the list is written on that stream just before, and the host waits between rounds.
-    lq.knob = env_frame_overlap() && !rb && !pl;
-    lq.device_out = out_dev != 0;
-    lq.persist = persist;
-    lq.shared_scratch = p.sc.wide_spill != nullptr;
-    lq.second_set = true;  // asked first whether the call would overlap at all; then whether the set can be had
-    lq.second_set = lane_plan(lq).overlap && lanes_ready(c, plan.partial_bytes);
-    // the run length of the queue's units (rt_plan.h RunPlan) is the knob's for a kernel that takes runs, else
-    // auto_run's (below, per launch), against the most lanes the device can hold (32 waves of 64 per CU)
-    const uint32_t forced_run = kernel_takes_runs(kind) ? env_item_run() : 1;
-    if (kernel_takes_runs(kind) && c->max_lanes == 0) {
-      int ncu = 0;
-      RT_HIP(c, hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->device));
-      c->max_lanes = (uint64_t)std::max(ncu, 1) * 2048u;
-    }
-    for (uint32_t c0 = 0; c0 < plan.nchunks; c0 += plan.cpp) {  // the passes (one for every BASELINE config but C5)
-      const uint32_t pc = std::min(plan.cpp, plan.nchunks - c0);
-      p.chunk0 = c0;
-      p.n_items = npix * pc;
-      lq.n = c->lane_launches;
-      lq.inputs_written = c->inputs_written;
-      lq.prev_overlapped = c->prev_overlapped;
-      lq.lane_stale[0] = c->lane_stale[0];
-      lq.lane_stale[1] = c->lane_stale[1];
-      const LanePlan lp = lane_plan(lq);
-      // runs only in a stream of overlapped launches, where the next launch hides this one's longer end (auto_run)
-      const uint32_t run =
-          forced_run ? forced_run : auto_run(plan, kind, spp, npix, c->max_lanes, lp.overlap && lq.prev_overlapped);
-      const RunPlan rp = plan_runs(plan, spp, c0, pc, npix, run);
-      p.n_units = rp.n_units;
-      p.run_cfg = run_cfg_pack(rp.runs, rp.run_log2);
-      const R* partial = (const R*)c->partial.ptr;
-      if (lp.overlap) {
-        hipStream_t lane = lp.lane ? c->lane1 : c->stream;
-        if (lp.set) {
-          p.partial = (R*)c->partial2.ptr;
-          p.heads = (uint32_t*)c->heads2.ptr;
-        } else {
-          p.partial = (R*)c->partial.ptr;
-          p.heads = (uint32_t*)c->heads.ptr;
-        }
-        partial = p.partial;
-        // outstanding from here on, the lanes included, whatever fails below
-        c->pending = true;
-        c->pend_stream = st;
-        c->lanes_live = true;
-        if (lp.wait_resolve) RT_HIP(c, hipStreamWaitEvent(lane, c->ev_resolved[lp.set], 0));
-        if (lp.record_inputs) {
-          RT_HIP(c, hipEventRecord(c->ev_inputs, st));
-          c->inputs_written = false;
-          c->lane_stale[0] = c->lane_stale[1] = true;  // neither lane is behind this event yet
-        }
-        if (lp.wait_inputs) {
-          RT_HIP(c, hipStreamWaitEvent(lane, c->ev_inputs, 0));
-          c->lane_stale[lp.lane] = false;
-        }
-        c->prev_overlapped = true;
-        c->lane_launches++;
-        if ((s = run_persistent(c, p, kind, nblk_max, lane, true)) != RT_OK) return s;
-        RT_HIP(c, hipEventRecord(c->ev_done[lp.lane], lane));
-        // The caller's stream takes the launch in here, before its resolve: `out` is written on the caller's stream
-        // alone, in the order of the calls, and whatever the caller queues behind this call (the next call's uploads
-        // among it) is behind every launch so far.
-        RT_HIP(c, hipStreamWaitEvent(st, c->ev_done[lp.lane], 0));
-      } else {
-        c->prev_overlapped = false;
-        c->inputs_written = false;  // the launch runs on the stream the inputs were queued on
-        s = persist ? run_persistent(c, p, kind, nblk_max, st) : run_wavefront(c, p, kind, nblk_max, st);
-        if (s != RT_OK) return s;
-      }
-      if (pl)
-        launch_resolve_moments<R>(partial, pl->slots, npix, pc, pl->acc, st);
-      else
-        launch_resolve<R>(partial, npix, pc, spp, (R*)dout, c0 == 0, c0 + pc >= plan.nchunks, st);
-      if (lp.overlap) RT_HIP(c, hipEventRecord(c->ev_resolved[lp.set], st));
-      c->last.launches++;
-      RT_HIP(c, hipGetLastError());
-    }
-    // device output: nothing waits here -- the segment counters (cumulative on the device), the
-    // timing events and the fault word are settled by rt_stats, rt_reset_counters or a host-output call
-    c->pending = true;
-    c->pend_stream = st;
-    c->last.samples += (uint64_t)npix * spp;
+    partial = p.partial;
+    // outstanding from here on, the lanes included, whatever fails below
+    mark_pending(c, st);
+    c->lanes_live = true;
+    if (lp.wait_resolve) RT_HIP(c, hipStreamWaitEvent(lane, c->ev_resolved[lp.set], 0));
+    if (lp.record_inputs) RT_HIP(c, hipEventRecord(c->ev_inputs, st));
+    if (lp.wait_inputs) RT_HIP(c, hipStreamWaitEvent(lane, c->ev_inputs, 0));
+    if ((s = run_persistent(c, p, rc.kind, rc.nblk_max, lane, true)) != RT_OK) return s;
+    RT_HIP(c, hipEventRecord(c->ev_done[lp.lane], lane));
+    // The caller's stream takes the launch in here, before its resolve: `out` is written on the caller's stream
+    // alone, in the order of the calls, and whatever the caller queues behind this call (the next call's uploads
+    // among it) is behind every launch so far.
+    RT_HIP(c, hipStreamWaitEvent(st, c->ev_done[lp.lane], 0));
+  } else {
+    s = rc.persist ? run_persistent(c, p, rc.kind, rc.nblk_max, st) : run_wavefront(c, p, rc.kind, rc.nblk_max, st);
+    if (s != RT_OK) return s;
   }
-  if (!out_dev) {
-    RT_HIP(c, hipMemcpyAsync(out, dout, out_elems * sizeof(R), hipMemcpyDeviceToHost, st));
-    RT_HIP(c, hipStreamSynchronize(st));
+  rc.src.template resolve<R>(partial, rc.npix, c0, pc, plan, rc.spp, rc.dout, st);
+  if (lp.overlap) RT_HIP(c, hipEventRecord(c->ev_resolved[lp.set], st));
+  c->last.launches++;
+  RT_HIP(c, hipGetLastError());
+  return RT_OK;
+}
+
+// Step: the end of a call. A host `out` is copied out and the call returns finished and settled.
+template <class R>
+rt_status finish_render(rt_context* c, const RenderCall<R>& rc, std::chrono::steady_clock::time_point t0) {
+  if (!rc.src.out_dev) {
+    RT_HIP(c, hipMemcpyAsync(rc.src.out, rc.dout, 3ull * rc.npix * sizeof(R), hipMemcpyDeviceToHost, rc.st));
+    RT_HIP(c, hipStreamSynchronize(rc.st));
+    rt_status s;
     if ((s = settle(c)) != RT_OK) return s;
   }
   c->last.last_render_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   return RT_OK;
+}
+
+// The path-traced pixels of `src` with the parameters `prm`, queued on `st`.
+template <class R>
+rt_status render(rt_context* c, const PixelSource& src, const rt_render_params* prm, hipStream_t st) {
+  const auto t0 = std::chrono::steady_clock::now();
+  RenderCall<R> rc{src, prm, st};
+  rt_status s;
+  if ((s = scene_to_device(c, sizeof(R) == 8, st, &rc.lq)) != RT_OK) return s;
+  uint64_t npix64 = 0;
+  const std::vector<uint4> tl = src.packed_tiles(npix64);
+  if (npix64 >= (1ull << 31)) return set_err(c, RT_ERR_INVALID_ARGUMENT, "too many pixels in one call");
+  rc.npix = (uint32_t)npix64;
+  if (rc.npix == 0) return RT_OK;
+  rc.dout = src.out;
+  if (!src.out_dev) {
+    if ((s = ensure(c, c->out_tmp, 3ull * rc.npix * sizeof(R))) != RT_OK) return s;
+    rc.dout = c->out_tmp.ptr;
+  }
+  if (prm->max_depth <= 0) {
+    if ((s = src.template depth0<R>(c, prm, rc.npix, rc.dout, st)) != RT_OK) return s;
+  } else {
+    if ((s = plan_call(c, rc)) != RT_OK) return s;
+    if ((s = path_buffers(c, rc)) != RT_OK) return s;
+    if ((s = src.expand_map(c, tl, rc.npix, st)) != RT_OK) return s;
+    if ((s = fill_params(c, rc)) != RT_OK) return s;
+    lane_setup(c, rc);
+    for (uint32_t c0 = 0; c0 < rc.plan.nchunks; c0 += rc.plan.cpp)  // the passes (one for every BASELINE config but C5)
+      if ((s = one_pass(c, rc, c0)) != RT_OK) return s;
+    // device output: nothing waits here -- the segment counters (cumulative on the device), the
+    // timing events and the fault word are settled by rt_stats, rt_reset_counters or a host-output call
+    mark_pending(c, st);
+    c->last.samples += (uint64_t)rc.npix * rc.spp;
+  }
+  return finish_render(c, rc, t0);
 }
 
 // ---------------------------------------------------------------- the query path
@@ -770,8 +736,7 @@ rt_status render(rt_context* c, const rt_camera_desc* cam, const rt_render_param
 // A build without the kernel of family `fam` refuses the call; what: "query", "occlusion" or "feature-buffer"
 rt_status query_kernel_built(rt_context* c, TraceFamily fam, const char* what) {
   if (family_built(trace_render_family(fam))) return RT_OK;
-  return set_err(c, RT_ERR_UNSUPPORTED,
-                 std::string("this build (RT_DEV_ONLY) has no ") + trace_family_name(fam) + " " + what + " kernel");
+  return set_err(c, RT_ERR_UNSUPPORTED, dev_only_lacks(std::string(trace_family_name(fam)) + " " + what + " kernel"));
 }
 
 // What a query or feature-buffer launch on `st` reads of the scene, in place: scene_to_device, then the (object,
@@ -785,8 +750,7 @@ rt_status query_scene(rt_context* c, bool f64, hipStream_t st) {
     if (!cs.ids.empty())
       RT_HIP(c, hipMemcpyAsync(c->ids.ptr, cs.ids.data(), cs.ids.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
     c->ids_dirty = false;
-    c->pending = true;
-    c->pend_stream = st;
+    mark_pending(c, st);
   }
   return RT_OK;
 }
@@ -826,8 +790,7 @@ struct HostOut {
 rt_status query_done(rt_context* c, hipStream_t st, bool counted, bool on_device, std::initializer_list<HostOut> outs) {
   RT_HIP(c, hipGetLastError());
   if (counted) c->last.launches++;
-  c->pending = true;
-  c->pend_stream = st;
+  mark_pending(c, st);
   if (on_device) return RT_OK;
   for (const HostOut& o : outs) RT_HIP(c, hipMemcpyAsync(o.host, o.dev, o.bytes, hipMemcpyDeviceToHost, st));
   RT_HIP(c, hipStreamSynchronize(st));
@@ -976,8 +939,7 @@ rt_status render_adaptive(rt_context* c, const rt_camera_desc* cam, const rt_ada
   const PathKernel kind = path_kernel(f64 ? c->scene.hdr64 : c->scene.hdr, sizeof(typename WWord<R>::T), cam->mode, true,
                                       prm->traversal == RT_TRAV_ORDERED, c->scene.stack_need);
   if (prm->max_depth > 0 && !family_built(kind.fam))  // (render() would say so too, after the records were cleared)
-    return set_err(c, RT_ERR_UNSUPPORTED,
-                   std::string("this build (RT_DEV_ONLY) has no ") + family_name(kind.fam) + " kernels");
+    return set_err(c, RT_ERR_UNSUPPORTED, dev_only_lacks(kind.fam));
   rt_status s;
   if ((s = wait_other_stream(c, st)) != RT_OK) return s;  // (the call writes the context's buffers from here on)
   const uint32_t nb = (npix + kBlock - 1) / kBlock;
@@ -998,8 +960,7 @@ rt_status render_adaptive(rt_context* c, const rt_camera_desc* cam, const rt_ada
     if ((s = stage(c, c->ad_err, 8ull * npix, sp.out_err)) != RT_OK) return s;
   }
   if ((s = pixel_map(c, tl, npix, st)) != RT_OK) return s;
-  c->pending = true;  // outstanding from here on, whatever fails below
-  c->pend_stream = st;
+  mark_pending(c, st);  // outstanding from here on, whatever fails below
   RT_HIP(c, hipMemsetAsync(c->ad_acc.ptr, 0, sizeof(AdaptiveAcc) * (size_t)npix, st));
   sp.acc = (AdaptiveAcc*)c->ad_acc.ptr;
   sp.blk = (uint32_t*)c->ad_blk.ptr;
@@ -1019,7 +980,7 @@ rt_status render_adaptive(rt_context* c, const rt_camera_desc* cam, const rt_ada
   for (int32_t have = 0;;) {
     rp.spp = have == 0 ? prm->min_spp : prm->step_spp;
     rp.first_sample = have;
-    if ((s = render<R>(c, cam, &rp, nullptr, 0, nullptr, 1, st, nullptr, &pl)) != RT_OK) return s;
+    if ((s = render<R>(c, PixelSource::of_list(cam, pl), &rp, st)) != RT_OK) return s;
     have += rp.spp;
     const bool last = have >= prm->max_spp;  // every pixel stops after this round: no next list, no count to wait for
     sp.pixmap = pl.pixmap;
@@ -1144,6 +1105,24 @@ rt_status by_precision(rt_context* c, int32_t precision, bool any_exception, F&&
   return guarded(c, any_exception, [&] { return precision == RT_PREC_F64 ? f(double()) : f(float()); });
 }
 
+// rt_dev_plan_kernel and rt_dev_plan_radiance: `desc` compiled on the host, and the tag of the kernel that
+// kernel_of(header, word bytes, ordered, stack need) chooses for it in buf[n]; "" for a descriptor that does not compile
+// or an unknown precision or traversal
+template <class F>
+void dev_plan_tag(const rt_scene_desc* desc, int32_t precision, int32_t traversal, char* buf, size_t n, F&& kernel_of) {
+  if (!buf || n == 0) return;
+  buf[0] = 0;
+  CompiledScene cs;
+  std::string err;
+  if (!desc || (precision != RT_PREC_F32 && precision != RT_PREC_F64) ||
+      (traversal != RT_TRAV_AUTO && traversal != RT_TRAV_ORDERED) || compile_scene(desc, &cs, &err) != RT_OK)
+    return;
+  const bool f64 = precision == RT_PREC_F64;
+  const size_t word_bytes = f64 ? sizeof(WWord<double>::T) : sizeof(WWord<float>::T);
+  const PathKernel k = kernel_of(f64 ? cs.hdr64 : cs.hdr, word_bytes, traversal == RT_TRAV_ORDERED, cs.stack_need);
+  std::snprintf(buf, n, "%s", path_kernel_tag(k, word_bytes).c_str());
+}
+
 }  // namespace
 
 // ====================================================================== C ABI
@@ -1183,8 +1162,12 @@ rt_status rt_context_create(int32_t device, rt_context** out) {
   if ((e = hipSetDevice(device)) != hipSuccess) return set_err(nullptr, RT_ERR_HIP, hipGetErrorString(e));
   if ((e = upload_sincos_table()) != hipSuccess)
     return set_err(nullptr, RT_ERR_HIP, std::string("sin/cos table: ") + hipGetErrorString(e));
+  int ncu = 0;
+  if ((e = hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device)) != hipSuccess)
+    return set_err(nullptr, RT_ERR_HIP, hipGetErrorString(e));
   auto* c = new rt_context;
   c->device = device;
+  c->ncu = ncu;
   if ((e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)) != hipSuccess) {
     delete c;
     return set_err(nullptr, RT_ERR_HIP, hipGetErrorString(e));
@@ -1208,23 +1191,18 @@ rt_status rt_context_create(int32_t device, rt_context** out) {
 void rt_context_destroy(rt_context* c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
-  // an outstanding device-output render still reads the buffers freed below (its fault word is
-  // dropped with the context: nobody is left to report it to)
+  // an outstanding device-output render still reads the buffers freed with the context below (its fault word
+  // is dropped with it: nobody is left to report it to)
   if (c->pending) (void)hipStreamSynchronize(c->pend_stream);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   if (c->lane1) (void)hipStreamSynchronize(c->lane1);
   for (hipEvent_t e : {c->ev_done[0], c->ev_done[1], c->ev_resolved[0], c->ev_resolved[1], c->ev_inputs})
     if (e) (void)hipEventDestroy(e);
   if (c->lane1) (void)hipStreamDestroy(c->lane1);
-  for (DevBuf* b : {&c->partial2, &c->heads2, &c->scene32, &c->scene64, &c->state, &c->partial, &c->pixmap, &c->queue0, &c->queue1, &c->blk, &c->wide_spill,
-                    &c->out_tmp, &c->counters, &c->camx, &c->heads, &c->tiles, &c->fault, &c->ids, &c->q_rays, &c->q_geom,
-                    &c->q_ids, &c->ad_acc, &c->ad_pix[0], &c->ad_pix[1], &c->ad_slot[0], &c->ad_slot[1], &c->ad_blk,
-                    &c->ad_spp, &c->ad_err, &c->dn_scratch})
-    if (b->ptr) (void)hipFree(b->ptr);
   for (hipEvent_t e : c->events) (void)hipEventDestroy(e);
   if (c->total_host) (void)hipHostFree(c->total_host);
   if (c->stream) (void)hipStreamDestroy(c->stream);
-  delete c;
+  delete c;  // (every DevBuf frees its memory)
 }
 
 const char* rt_last_error(const rt_context* c) {
@@ -1261,7 +1239,7 @@ rt_status rt_scene_check(const rt_scene_desc* desc, rt_scene_info* info, char* e
     const KernelFamily fam = kernel_family(cs.hdr, RT_CAM_PERSPECTIVE, true, false);
     if (!family_built(fam)) {
       s = RT_ERR_UNSUPPORTED;
-      m = std::string("this build (RT_DEV_ONLY) has no ") + family_name(fam) + " kernels";
+      m = dev_only_lacks(fam);
     }
   }
   if (err && errlen > 0) std::snprintf(err, (size_t)errlen, "%s", m.c_str());
@@ -1302,7 +1280,7 @@ rt_status rt_render_tiles(rt_context* c, const rt_camera_desc* cam, const rt_ren
   RT_HIP(c, hipSetDevice(c->device));
   hipStream_t st = call_stream(c, stream, out_is_device != 0);
   return by_precision(c, prm->precision, true, [&](auto r) {
-    return render<decltype(r)>(c, cam, prm, tiles, ntiles, out_rgb, out_is_device, st);
+    return render<decltype(r)>(c, PixelSource::of_tiles(cam, tiles, ntiles, out_rgb, out_is_device != 0), prm, st);
   });
 }
 
@@ -1372,7 +1350,7 @@ rt_status rt_radiance(rt_context* c, const rt_radiance_params* prm, const double
   rp.traversal = prm->traversal;
   const RayBatch rb{rays, (uint32_t)nrays, prm->ray_base, prm->on_device != 0};
   return by_precision(c, prm->precision, true, [&](auto r) {
-    return render<decltype(r)>(c, nullptr, &rp, nullptr, 0, out_rgb, prm->on_device, st, &rb);
+    return render<decltype(r)>(c, PixelSource::of_rays(rb, out_rgb, prm->on_device != 0), &rp, st);
   });
 }
 
@@ -1517,33 +1495,16 @@ uint32_t rt_rng_u32(uint64_t seed, uint32_t pixel, uint32_t sample, uint32_t dim
 // rt_dev_last_kernel: for tests and scripts, not in rt_hip.h.
 void rt_dev_plan_kernel(const rt_scene_desc* desc, int32_t cam_mode, int32_t precision, int32_t traversal,
                         int32_t segments_per_launch, char* buf, size_t n) {
-  if (!buf || n == 0) return;
-  buf[0] = 0;
-  CompiledScene cs;
-  std::string err;
-  if (!desc || (precision != RT_PREC_F32 && precision != RT_PREC_F64) ||
-      (traversal != RT_TRAV_AUTO && traversal != RT_TRAV_ORDERED) || compile_scene(desc, &cs, &err) != RT_OK)
-    return;
-  const bool f64 = precision == RT_PREC_F64;
-  const size_t word_bytes = f64 ? sizeof(WWord<double>::T) : sizeof(WWord<float>::T);
-  const PathKernel k = path_kernel(f64 ? cs.hdr64 : cs.hdr, word_bytes, cam_mode, segments_per_launch <= 0,
-                                   traversal == RT_TRAV_ORDERED, cs.stack_need);
-  std::snprintf(buf, n, "%s", path_kernel_tag(k, word_bytes).c_str());
+  dev_plan_tag(desc, precision, traversal, buf, n, [&](const SceneHeader& h, size_t word_bytes, bool ordered, auto need) {
+    return path_kernel(h, word_bytes, cam_mode, segments_per_launch <= 0, ordered, need);
+  });
 }
 // The same for rt_radiance on a scene of `desc` (radiance_kernel): the tag a perspective render's kernel has, with
 // "rays" before the schedule.
 void rt_dev_plan_radiance(const rt_scene_desc* desc, int32_t precision, int32_t traversal, char* buf, size_t n) {
-  if (!buf || n == 0) return;
-  buf[0] = 0;
-  CompiledScene cs;
-  std::string err;
-  if (!desc || (precision != RT_PREC_F32 && precision != RT_PREC_F64) ||
-      (traversal != RT_TRAV_AUTO && traversal != RT_TRAV_ORDERED) || compile_scene(desc, &cs, &err) != RT_OK)
-    return;
-  const bool f64 = precision == RT_PREC_F64;
-  const size_t word_bytes = f64 ? sizeof(WWord<double>::T) : sizeof(WWord<float>::T);
-  const PathKernel k = radiance_kernel(f64 ? cs.hdr64 : cs.hdr, word_bytes, traversal == RT_TRAV_ORDERED, cs.stack_need);
-  std::snprintf(buf, n, "%s", path_kernel_tag(k, word_bytes).c_str());
+  dev_plan_tag(desc, precision, traversal, buf, n, [](const SceneHeader& h, size_t word_bytes, bool ordered, auto need) {
+    return radiance_kernel(h, word_bytes, ordered, need);
+  });
 }
 
 }  // extern "C"

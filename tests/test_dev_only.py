@@ -28,8 +28,9 @@ for name, want in (("cornell_box", abi.RT_OK), ("rtow", abi.RT_ERR_UNSUPPORTED),
 '''
 
 
-SRCS = ("rt_kernels.hip", "rt_render.hip", "rt_multi.hip", "scene_compile.cpp", "rt_device.h", "rt_types.h",
-        "rt_launch.h", "rt_plan.h", "rt_scene.h", "rt_sin.h", "scene_compile.h")
+# the four compiled sources, then every header they read (the Makefile's LIB_HDRS; include/rt_hip.h is added below)
+SRCS = ("rt_kernels.hip", "rt_render.hip", "rt_multi.hip", "scene_compile.cpp", "rt_device.h", "rt_room.h", "rt_types.h",
+        "rt_launch.h", "rt_context.h", "rt_plan.h", "rt_denoise.h", "rt_denoise.hip", "rt_sin.h", "rt_scene.h", "scene_compile.h")
 
 
 def dev_build():

@@ -361,3 +361,31 @@ def test_renders_and_batches_interleave(ctx, refs, prec):
     assert img0.max() > 0 and rad0.max() > 0
     assert np.array_equal(img0, img1) and np.array_equal(rad0, rad1) and np.array_equal(rad0, rad2)
     assert np.array_equal(tiles, img0[5:14, 3:10].reshape(-1, 3))
+
+
+@pytest.mark.parametrize("prec", BOTH, ids=P.get)
+def test_a_batch_between_overlapped_renders(ctx, refs, prec):
+    """Device-output renders queued back to back keep the launch lanes live; a device-output batch between them is a
+    serial launch on the caller's stream that writes buffer set 0. Every result is, bit for bit, what it is alone."""
+    import torch
+    desc, cam, rays, _ = refs("mesh_ll")
+    ctx.upload(desc)
+    alone = ctx.render(cam, 4, DEPTH, seed=SEED, precision=prec)
+    host = ctx.radiance(rays, 4, DEPTH, seed=SEED, precision=prec)
+    assert alone.max() > 0 and host.max() > 0
+    dev = torch.device(f"cuda:{ctx.device}")
+    dt = torch.float64 if prec == F64 else torch.float32
+    bufs = [torch.zeros(alone.shape, dtype=dt, device=dev) for _ in range(6)]
+    drays = torch.from_numpy(rays.copy()).to(dev)
+    prm = ctx.params(4, DEPTH, SEED, prec)
+    stream = ctx._torch_stream(None, dev)
+    tl = abi.TileList([(0, 0, cam.image_width, cam.image_height)])
+    for b in bufs[:3]:
+        ctx.render_tiles(cam, prm, tl, b.data_ptr(), True, stream)
+    batch = ctx.radiance(drays, 4, DEPTH, seed=SEED, precision=prec)
+    for b in bufs[3:]:
+        ctx.render_tiles(cam, prm, tl, b.data_ptr(), True, stream)
+    torch.cuda.synchronize()
+    for k, b in enumerate(bufs):
+        assert np.array_equal(b.cpu().numpy(), alone), k
+    assert np.array_equal(batch.cpu().numpy(), host)

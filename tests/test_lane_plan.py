@@ -1,6 +1,8 @@
 """The ordering of overlapped persistent launches without a GPU: csrc/rt_plan.h lane_plan, the one function that
-says which lane and buffer set a launch takes and what it waits for (tests/native/lane_plan_dump.cpp). The context's
-bookkeeping between launches (render<R> in csrc/rt_render.hip) is replayed here in a few lines."""
+says which lane and buffer set a launch takes and what it waits for, and lane_advance, the one function that says
+what a launch leaves in the context's LaneState for the next. tests/native/lane_plan_dump.cpp runs both: its stateful
+mode holds the LaneState across launches exactly as a context does (render<R> in csrc/rt_render.hip calls the same two
+functions), so nothing of the bookkeeping is repeated here."""
 import os
 import subprocess
 
@@ -9,6 +11,8 @@ import pytest
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(REPO, "cpu-ray-tracing-implementation_amd", "csrc")
 KEYS = ("overlap", "lane", "set", "sync_prev", "wait_resolve", "record_inputs", "wait_inputs")
+STATE = ("n", "inputs_written", "prev_overlapped", "stale0", "stale1")
+CALL = dict(knob=1, device_out=1, persist=1, shared_scratch=0, second_set=1)
 
 
 @pytest.fixture(scope="module")
@@ -17,40 +21,39 @@ def ask(tmp_path_factory):
     subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", "-I", CSRC, "-o", exe,
                     os.path.join(REPO, "tests", "native", "lane_plan_dump.cpp")], check=True)
 
+    def answers(lines):
+        out = subprocess.run([exe], input="".join(lines), check=True, capture_output=True, text=True).stdout
+        return [[int(v) for v in row.split()] for row in out.splitlines()]
+
     def run(**q):
-        d = dict(knob=1, device_out=1, persist=1, shared_scratch=0, second_set=1, n=0, inputs_written=0,
-                 prev_overlapped=0, stale0=0, stale1=0, pending=0, caller=0, prev=0)
+        d = dict(CALL, n=0, inputs_written=0, prev_overlapped=0, stale0=0, stale1=0, pending=0, caller=0, prev=0)
         assert set(q) <= set(d)
         d.update(q)
-        line = "L " + " ".join(str(int(v)) for v in d.values()) + "\n"
-        out = subprocess.run([exe], input=line, check=True, capture_output=True, text=True).stdout.split()
-        return dict(zip(KEYS, (int(v) for v in out)))
+        return dict(zip(KEYS, answers(["L " + " ".join(str(int(v)) for v in d.values()) + "\n"])[0]))
+    run.answers = answers
     return run
 
 
 class Ctx:
-    """What a context remembers between launches, updated as render<R> updates it."""
+    """A context's launches, one stateful line each. The lanes' state lives in the dump program (all lines so far are
+    replayed into a fresh process per launch); this keeps only what is outside it: the mirror of pending / pend_stream."""
 
     def __init__(self, ask):
-        self.ask, self.n, self.inputs, self.prev_ov, self.stale = ask, 0, 0, 0, [0, 0]
+        self.ask, self.lines, self.reported = ask, [], dict.fromkeys(STATE, 0)
         self.pending, self.prev = 0, 0
 
+    @property
+    def n(self):
+        return self.reported["n"]
+
     def launch(self, caller=0, write=False, **kw):
-        if write:
-            self.inputs = 1
-        p = self.ask(n=self.n, inputs_written=self.inputs, prev_overlapped=self.prev_ov, stale0=self.stale[0],
-                     stale1=self.stale[1], pending=self.pending, caller=caller, prev=self.prev, **kw)
-        if p["overlap"]:
-            if p["record_inputs"]:
-                self.inputs, self.stale = 0, [1, 1]
-            if p["wait_inputs"]:
-                self.stale[p["lane"]] = 0
-            self.prev_ov = 1
-            self.n += 1
-        else:
-            self.prev_ov, self.inputs = 0, 0
+        assert set(kw) <= set(CALL)
+        d = dict(CALL, **kw, pending=self.pending, caller=caller, prev=self.prev, write=write)
+        self.lines.append("S " + " ".join(str(int(v)) for v in d.values()) + "\n")
+        row = self.ask.answers(self.lines)[-1]
+        self.reported = dict(zip(STATE, row[len(KEYS):]))
         self.pending, self.prev = 1, caller
-        return p
+        return dict(zip(KEYS, row))
 
 
 def test_first_two_launches_and_steady_state(ask):
@@ -119,3 +122,22 @@ def test_a_serial_launch_between_overlapped_ones_is_waited_for(ask):
     assert (p["overlap"], p["lane"], p["record_inputs"], p["wait_inputs"], p["wait_resolve"]) == (1, 1, 1, 1, 1)
     p = c.launch()
     assert (p["lane"], p["record_inputs"], p["wait_inputs"]) == (0, 0, 1)
+
+
+def test_serial_launches_after_overlapped_ones_leave_the_lanes_as_they_were(ask):
+    # read off render<R>: a serial launch clears prev_overlapped and inputs_written (it runs on the stream the inputs
+    # were queued on) and touches neither the lanes' launch count nor their staleness
+    c = Ctx(ask)
+    for _ in range(4):
+        c.launch()
+    c.launch(write=True)  # lane 0 records the inputs event and waits for it: lane 1 is stale
+    assert c.reported == dict(n=5, inputs_written=0, prev_overlapped=1, stale0=0, stale1=1)
+    assert c.launch(knob=0)["overlap"] == 0
+    lone = dict(n=5, inputs_written=0, prev_overlapped=0, stale0=0, stale1=1)
+    assert c.reported == lone
+    assert c.launch(knob=0, write=True)["overlap"] == 0  # a write, and another serial launch
+    assert c.reported == lone
+    # ... and the lanes go on from there: the next overlapped launch is the sixth, behind a new inputs event
+    p = c.launch()
+    assert p == dict(overlap=1, lane=1, set=1, sync_prev=0, wait_resolve=1, record_inputs=1, wait_inputs=1)
+    assert c.reported == dict(n=6, inputs_written=0, prev_overlapped=1, stale0=1, stale1=0)
