@@ -14,9 +14,10 @@ ARCH     ?= gfx950
 HIPFLAGS ?= -O3 -std=c++17 -fPIC -Wall -ffp-contract=on -fno-slp-vectorize --offload-arch=$(ARCH)
 
 LIB_SRCS := $(PKG)/csrc/rt_kernels.hip $(PKG)/csrc/rt_render.hip $(PKG)/csrc/rt_multi.hip $(PKG)/csrc/scene_compile.cpp
-# (csrc/rt_denoise.hip, the denoiser's kernels, is compiled as part of rt_render.hip, which includes it: the library
-# stays the four translation units its development variants and tests/test_dev_only.py build)
-LIB_HDRS := $(PKG)/csrc/rt_device.h $(PKG)/csrc/rt_room.h $(PKG)/csrc/rt_types.h $(PKG)/csrc/rt_launch.h $(PKG)/csrc/rt_context.h $(PKG)/csrc/rt_plan.h $(PKG)/csrc/rt_denoise.h $(PKG)/csrc/rt_denoise.hip $(PKG)/csrc/rt_sin.h $(PKG)/csrc/rt_scene.h $(PKG)/csrc/scene_compile.h include/rt_hip.h
+# (csrc/rt_denoise.hip, the denoiser's kernels, and csrc/rt_temporal.hip, the temporal accumulation's, are compiled as
+# part of rt_render.hip, which includes them: the library stays the four translation units its development variants and
+# tests/test_dev_only.py build)
+LIB_HDRS := $(PKG)/csrc/rt_device.h $(PKG)/csrc/rt_room.h $(PKG)/csrc/rt_types.h $(PKG)/csrc/rt_launch.h $(PKG)/csrc/rt_context.h $(PKG)/csrc/rt_plan.h $(PKG)/csrc/rt_denoise.h $(PKG)/csrc/rt_denoise.hip $(PKG)/csrc/rt_temporal.h $(PKG)/csrc/rt_temporal.hip $(PKG)/csrc/rt_sin.h $(PKG)/csrc/rt_scene.h $(PKG)/csrc/scene_compile.h include/rt_hip.h
 
 CXX      ?= g++
 CXXFLAGS ?= -O2 -std=c++17 -fPIC -Wall -Wextra -Wno-unused-parameter

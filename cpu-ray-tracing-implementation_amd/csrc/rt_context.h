@@ -84,7 +84,8 @@ struct rt_context {
   // copies of a host-pointer call's out_spp and out_err (out_rgb's is out_tmp)
   DevBuf ad_acc, ad_pix[2], ad_slot[2], ad_blk, ad_spp, ad_err;
   // denoising (rt_denoise): the working records, kDnScratchT T a pixel; a host-pointer call's inputs and output are
-  // staged in out_tmp (rgb, in and out), q_rays (feat) and q_geom (var)
+  // staged in out_tmp (rgb, in and out), q_rays (feat) and q_geom (var). A host-pointer rt_temporal stages the same way,
+  // its ids in q_ids and its two histories in dn_scratch (it has no working records of its own)
   DevBuf dn_scratch;
 };
 

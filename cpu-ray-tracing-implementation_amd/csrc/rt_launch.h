@@ -8,6 +8,7 @@
 
 #include "rt_denoise.h"
 #include "rt_plan.h"
+#include "rt_temporal.h"
 #include "rt_types.h"
 
 namespace rtd __attribute__((visibility("hidden"))) {
@@ -239,6 +240,14 @@ void launch_camera_rays(const CamRayParams& p, hipStream_t st);
 template <class T>
 void launch_denoise(const rt_denoise_params& prm, const T* rgb_in, const double* feat, const double* var, T* scratch,
                     T* rgb_out, hipStream_t st);
+
+// ---- temporal accumulation (rt_temporal; the kernel is rt_temporal.hip's): one launch on `st`. Checked parameters and
+// cameras; the pointers as rt_temporal takes them, on the device (ids, var, hist_in and var_out may be null, rgb_out
+// may be rgb_in and var_out var).
+template <class T>
+void launch_temporal(const rt_temporal_params& prm, const rt_camera_desc* cam, const rt_camera_desc* prev,
+                     const T* rgb_in, const double* feat, const int32_t* ids, const double* var, const void* hist_in,
+                     void* hist_out, T* rgb_out, double* var_out, hipStream_t st);
 
 // the fp64 sin/cos table (rt_device.h g_sincos_tab) copied to the calling thread's device
 hipError_t upload_sincos_table();

@@ -5,11 +5,11 @@
 //    (rt_radiance) or a camera's pixel list (a round of rt_render_adaptive) -- as a list of named steps, of which
 //    one_pass() is the only one that launches a path kernel;
 //  - the query path (trace_rays<R>(), occluded<R>(), camera_rays(), render_aov<R>()), the round loop of
-//    rt_render_adaptive (render_adaptive<R>()) and denoise<T>();
+//    rt_render_adaptive (render_adaptive<R>()), denoise<T>() and temporal<T>();
 //  - the C ABI of include/rt_hip.h with its argument checks.
 // It contains no kernel of its own: what a render launches goes through rt_launch.h (rt_kernels.hip), and its item
-// layout, kernel family and lane ordering come from rt_plan.h. (The denoiser's kernels, rt_denoise.hip, are included at
-// the end, so that the library stays four translation units.)
+// layout, kernel family and lane ordering come from rt_plan.h. (The denoiser's kernels, rt_denoise.hip, and the temporal
+// accumulation's, rt_temporal.hip, are included at the end, so that the library stays four translation units.)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -1032,6 +1032,44 @@ rt_status denoise(rt_context* c, const rt_denoise_params* prm, const void* rgb_i
   return query_done(c, st, false, prm->on_device != 0, {{rgb_out, out, npix * 3 * sizeof(T)}});
 }
 
+// rt_temporal for one precision: checked parameters, cameras and pointers, whole image. A pixel reads its own rgb and
+// var before it writes them, so rgb_out may be rgb_in and var_out var. A host-pointer call stages the frame in the
+// buffers rt_denoise's stages it in, the ids in q_ids and the two histories, one after the other, in dn_scratch.
+template <class T>
+rt_status temporal(rt_context* c, const rt_temporal_params* prm, const rt_camera_desc* cam,
+                   const rt_camera_desc* prev_cam, const void* rgb_in, const double* feat, const int32_t* ids,
+                   const double* var, const void* hist_in, void* hist_out, void* rgb_out, double* var_out,
+                   hipStream_t st) {
+  const size_t npix = (size_t)prm->width * (size_t)prm->height;
+  const size_t hb = tp_history_bytes(npix, sizeof(T) == 8), hb_step = (hb + 255) / 256 * 256;
+  rt_status s;
+  if ((s = wait_other_stream(c, st)) != RT_OK) return s;  // (a call on another stream may still use the staging buffers)
+  if (prm->on_device) {
+    launch_temporal<T>(*prm, cam, prev_cam, (const T*)rgb_in, feat, ids, var, hist_in, hist_out, (T*)rgb_out, var_out, st);
+    return query_done(c, st, true, true, {});
+  }
+  T* d_rgb = nullptr;
+  double *d_feat = nullptr, *d_var = nullptr;
+  int32_t* d_ids = nullptr;
+  unsigned char* d_hist = nullptr;
+  if ((s = stage(c, c->out_tmp, npix * 3 * sizeof(T), d_rgb)) != RT_OK) return s;
+  if ((s = stage(c, c->q_rays, npix * 64, d_feat)) != RT_OK) return s;
+  if ((var || var_out) && (s = stage(c, c->q_geom, npix * 8, d_var)) != RT_OK) return s;
+  if (ids && (s = stage(c, c->q_ids, npix * 16, d_ids)) != RT_OK) return s;
+  if ((s = stage(c, c->dn_scratch, 2 * hb_step, d_hist)) != RT_OK) return s;
+  RT_HIP(c, hipMemcpyAsync(d_rgb, rgb_in, npix * 3 * sizeof(T), hipMemcpyHostToDevice, st));
+  RT_HIP(c, hipMemcpyAsync(d_feat, feat, npix * 64, hipMemcpyHostToDevice, st));
+  if (var) RT_HIP(c, hipMemcpyAsync(d_var, var, npix * 8, hipMemcpyHostToDevice, st));
+  if (ids) RT_HIP(c, hipMemcpyAsync(d_ids, ids, npix * 16, hipMemcpyHostToDevice, st));
+  if (hist_in) RT_HIP(c, hipMemcpyAsync(d_hist, hist_in, hb, hipMemcpyHostToDevice, st));
+  launch_temporal<T>(*prm, cam, prev_cam, d_rgb, d_feat, d_ids, var ? d_var : nullptr, hist_in ? d_hist : nullptr,
+                     d_hist + hb_step, d_rgb, var_out ? d_var : nullptr, st);
+  if (var_out)
+    return query_done(c, st, true, false,
+                      {{rgb_out, d_rgb, npix * 3 * sizeof(T)}, {var_out, d_var, npix * 8}, {hist_out, d_hist + hb_step, hb}});
+  return query_done(c, st, true, false, {{rgb_out, d_rgb, npix * 3 * sizeof(T)}, {hist_out, d_hist + hb_step, hb}});
+}
+
 // ---------------------------------------------------------------- argument checks of the C entry points
 // Each check is written once; every entry point calls the ones it has in its own order (which error wins when several
 // apply differs between them, and stays: tests/test_gpu_query_contract.py).
@@ -1451,6 +1489,30 @@ rt_status rt_denoise(rt_context* c, const rt_denoise_params* prm, const void* rg
   });
 }
 
+// (rt_temporal_check, rt_temporal_history_bytes and rt_dev_temporal_host, which need no context: rt_temporal.hip)
+rt_status rt_temporal(rt_context* c, const rt_temporal_params* prm, const rt_camera_desc* cam,
+                      const rt_camera_desc* prev_cam, const void* rgb_in, const double* feat, const int32_t* ids,
+                      const double* var, const void* hist_in, void* hist_out, void* rgb_out, double* var_out,
+                      void* stream) {
+  // (the context last, as in rt_denoise)
+  if (!prm || !cam || !rgb_in || !feat || !hist_out || !rgb_out || (hist_in && !prev_cam))
+    return set_err(c, RT_ERR_INVALID_ARGUMENT, "null argument");
+  const char* m = nullptr;
+  if (const rt_status s = temporal_check(prm, cam, hist_in ? prev_cam : nullptr, &m)) return set_err(c, s, m);
+  if (hist_in && tp_overlap(hist_in, hist_out,
+                            tp_history_bytes((size_t)prm->width * (size_t)prm->height, prm->precision == RT_PREC_F64)))
+    return set_err(c, RT_ERR_INVALID_ARGUMENT, "hist_in and hist_out overlap");
+  if (!c) return set_err(nullptr, RT_ERR_INVALID_ARGUMENT, "null context");
+  if (prm->on_device && ((uintptr_t)rgb_in | (uintptr_t)feat | (uintptr_t)ids | (uintptr_t)var | (uintptr_t)hist_in |
+                         (uintptr_t)hist_out | (uintptr_t)rgb_out | (uintptr_t)var_out) % 16 != 0)
+    return set_err(c, RT_ERR_INVALID_ARGUMENT, "device pointers must be 16-byte aligned");
+  return by_precision(c, prm->precision, false, [&](auto r) -> rt_status {
+    RT_HIP(c, hipSetDevice(c->device));
+    hipStream_t st = call_stream(c, stream, prm->on_device != 0);
+    return temporal<decltype(r)>(c, prm, cam, prev_cam, rgb_in, feat, ids, var, hist_in, hist_out, rgb_out, var_out, st);
+  });
+}
+
 int32_t rt_trace_family(rt_context* c, int32_t precision, int32_t traversal) {
   if (!c || !c->has_scene || (precision != RT_PREC_F32 && precision != RT_PREC_F64) ||
       (traversal != RT_TRAV_AUTO && traversal != RT_TRAV_ORDERED))
@@ -1512,3 +1574,5 @@ void rt_dev_plan_radiance(const rt_scene_desc* desc, int32_t precision, int32_t 
 // The denoiser's kernels, their launch function and its two host-only entry points: a file of their own, compiled as
 // part of this translation unit, so that the library stays the four sources every build of it lists.
 #include "rt_denoise.hip"
+// ... and rt_temporal's kernel with its three host-only entry points, the same way.
+#include "rt_temporal.hip"

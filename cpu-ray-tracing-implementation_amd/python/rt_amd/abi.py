@@ -116,6 +116,15 @@ class rt_denoise_params(ctypes.Structure):
                 ("sigma_depth", c_double), ("albedo_eps", c_double), ("color_eps", c_double), ("depth_eps", c_double)]
 
 
+RT_TEMPORAL_DEMODULATE = 1
+
+
+class rt_temporal_params(ctypes.Structure):
+    _fields_ = [("width", c_int32), ("height", c_int32), ("precision", c_int32), ("on_device", c_int32),
+                ("flags", c_int32), ("max_history", c_int32), ("alpha_min", c_double), ("depth_tol", c_double),
+                ("normal_cos", c_double), ("min_weight", c_double), ("albedo_eps", c_double)]
+
+
 # rt_trace_family_kind
 RT_TRACE_FLAT, RT_TRACE_LINEAR, RT_TRACE_WIDE_LDS, RT_TRACE_WIDE_HBM, RT_TRACE_STACK = range(5)
 TRACE_FAMILY_NAMES = ("FLAT", "LINEAR", "WIDE_LDS", "WIDE_HBM", "STACK")
@@ -158,6 +167,10 @@ SIGNATURES = {
     "rt_denoise_check": (c_int32, [ctypes.POINTER(rt_denoise_params), ctypes.c_char_p, ctypes.c_size_t]),
     "rt_denoise": (c_int32, [ctypes.c_void_p, ctypes.POINTER(rt_denoise_params), ctypes.c_void_p, ctypes.c_void_p,
                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "rt_temporal_check": (c_int32, [ctypes.POINTER(rt_temporal_params), ctypes.POINTER(rt_camera_desc),
+                                    ctypes.POINTER(rt_camera_desc), ctypes.c_char_p, ctypes.c_size_t]),
+    "rt_temporal": (c_int32, [ctypes.c_void_p, ctypes.POINTER(rt_temporal_params), ctypes.POINTER(rt_camera_desc),
+                              ctypes.POINTER(rt_camera_desc)] + [ctypes.c_void_p] * 9),
     "rt_multi_create": (c_int32, [ctypes.POINTER(c_int32), c_int32, ctypes.POINTER(ctypes.c_void_p)]),
     "rt_multi_destroy": (None, [ctypes.c_void_p]),
     "rt_multi_last_error": (ctypes.c_char_p, [ctypes.c_void_p]),
@@ -236,6 +249,14 @@ def load():
         lib.rt_dev_denoise_host.restype = c_int32
         lib.rt_dev_denoise_host.argtypes = [ctypes.POINTER(rt_denoise_params), ctypes.c_void_p, ctypes.c_void_p,
                                             ctypes.c_void_p, ctypes.c_void_p]
+        # rt_temporal_history_bytes: the header declares it, but it is the one function there that returns a size_t, a
+        # return type tests/test_boundary.py's scan of the header does not know, so it is bound here and not in SIGNATURES
+        lib.rt_temporal_history_bytes.restype = ctypes.c_size_t
+        lib.rt_temporal_history_bytes.argtypes = [c_int32, c_int32, c_int32]
+        # ... and rt_temporal as a host loop over the kernel's own arithmetic (no GPU): rt_amd.temporal_host
+        lib.rt_dev_temporal_host.restype = c_int32
+        lib.rt_dev_temporal_host.argtypes = [ctypes.POINTER(rt_temporal_params), ctypes.POINTER(rt_camera_desc),
+                                             ctypes.POINTER(rt_camera_desc)] + [ctypes.c_void_p] * 8
         if lib.rt_abi_version() != ABI_VERSION:
             raise RuntimeError(f"{path} has ABI {lib.rt_abi_version()}, this binding expects {ABI_VERSION}: rebuild")
         _lib = lib

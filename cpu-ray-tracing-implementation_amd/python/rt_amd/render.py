@@ -301,6 +301,50 @@ class Context:
                                         None if var is None else ptr(var), ptr(out), sp))
         return out
 
+    def temporal(self, cam, prev_cam, rgb, aov, var=None, ids=None, hist=None, alpha_min=0.05, max_history=64,
+                 depth_tol=0.05, normal_cos=0.9, min_weight=0.25, demodulate=True, albedo_eps=1e-2, stream=None,
+                 hist_out=None):
+        """The frame `rgb`, (H, W, 3) float32 or float64, blended with the accumulated frames before it (rt_temporal):
+        `hist`, the "hist" of the call before (None: a first frame), is reprojected from `prev_cam` into `cam` through
+        this frame's guides `aov` (as Context.denoise takes them), history that no longer shows the same surface is
+        rejected, and the rest is blended with weight max(alpha_min, 1 / (N + 1)). `var`: (H, W) float64 as for denoise,
+        or None; `ids`: render_aov's "ids", (H, W, 4) int32, or None. The precision is rgb's dtype. Needs no scene.
+        -> dict(rgb (H, W, 3), var (H, W) float64 -- what denoise takes as var --, hist, a uint8 buffer of
+        rt_temporal_history_bytes bytes to hand to the next call, count (H, W), a view of hist's N plane).
+
+        `hist_out`: a buffer of hist's kind and size to write the new history into (not `hist` itself: the call reads
+        one while it writes the other), for a caller that keeps two and swaps them; None: a new one.
+        With a still camera pass normal_cos = -1 (progressive rendering): a guide normal is a mean over the pixel's
+        samples, shorter than 1 where the pixel straddles an edge, and the default 0.9 drops such a pixel's history.
+
+        numpy inputs take the host path; torch tensors on the context's device take the device path, ordered on
+        `stream` (default torch's current stream). All arrays are of one kind."""
+        dev = None if isinstance(rgb, np.ndarray) else rgb.device
+        if dev is not None:
+            import torch
+            if not (isinstance(rgb, torch.Tensor) and rgb.is_cuda and rgb.device.index == self.device):
+                raise ValueError("rgb: a numpy array or a torch tensor on the context's device")
+        prm, rgb, aov, var, ids, hist, ptr = _temporal_inputs(rgb, aov, var, ids, hist, int(dev is not None), alpha_min,
+                                                              max_history, depth_tol, normal_cos, min_weight,
+                                                              demodulate, albedo_eps)
+        H, W = prm.height, prm.width
+        if hist_out is not None and not (isinstance(hist_out, type(rgb)) and hist_out.dtype == (np if dev is None else torch).uint8 and
+                                         hist_out.ndim == 1 and int(hist_out.shape[0]) == _history_bytes(prm) and
+                                         (dev is None or hist_out.device == dev) and
+                                         (hist_out.flags.c_contiguous if dev is None else hist_out.is_contiguous())):
+            raise ValueError("hist_out: a contiguous uint8 buffer of hist's kind and size")
+        if dev is None:
+            out, var_out = np.empty_like(rgb), np.empty((H, W), np.float64)
+            hist_out = np.empty(_history_bytes(prm), np.uint8) if hist_out is None else hist_out
+        else:
+            out, var_out = torch.empty_like(rgb), torch.empty((H, W), dtype=torch.float64, device=dev)
+            hist_out = torch.empty(_history_bytes(prm), dtype=torch.uint8, device=dev) if hist_out is None else hist_out
+        sp = None if dev is None else self._torch_stream(stream, dev)
+        self._check(self.lib.rt_temporal(self.h, ctypes.byref(prm), ctypes.byref(cam),
+                                         None if prev_cam is None else ctypes.byref(prev_cam), ptr(rgb), ptr(aov),
+                                         ptr(ids), ptr(var), ptr(hist), ptr(hist_out), ptr(out), ptr(var_out), sp))
+        return dict(rgb=out, var=var_out, hist=hist_out, count=history_planes(hist_out, W, H, rgb.dtype)["count"])
+
     @staticmethod
     def _stream_handle(stream):
         return int(getattr(stream, "cuda_stream", stream) or 0)
@@ -385,6 +429,120 @@ def denoise_host(rgb, feat, var=None, iterations=5, sigma_color=2.0, sigma_norma
     if st != abi.RT_OK:
         raise abi.RTError(st, "rt_dev_denoise_host: parameters rt_denoise_check refuses")
     return out
+
+
+def _history_bytes(prm):
+    return int(abi.load().rt_temporal_history_bytes(prm.width, prm.height, prm.precision))
+
+
+def _temporal_inputs(rgb, aov, var, ids, hist, on_device, alpha_min, max_history, depth_tol, normal_cos, min_weight,
+                     demodulate, albedo_eps):
+    """What Context.temporal and temporal_host make of their arrays: (the parameters, the five arrays contiguous and
+    checked -- aov as (npix, 8) rows --, the function that gives an array's pointer, None for None)."""
+    if isinstance(rgb, np.ndarray):
+        f64, f32, i32, u8, cat, contiguous = np.float64, np.float32, np.int32, np.uint8, np.concatenate, np.ascontiguousarray
+        ptr = lambda a: None if a is None else a.ctypes.data
+    else:
+        import torch
+        f64, f32, i32, u8, cat = torch.float64, torch.float32, torch.int32, torch.uint8, torch.cat
+        contiguous = lambda a: a.contiguous()
+        ptr = lambda a: None if a is None else a.data_ptr()
+    if rgb.ndim != 3 or rgb.shape[2] != 3 or rgb.dtype not in (f32, f64):
+        raise ValueError("rgb: an (H, W, 3) float32 or float64 array or tensor")
+    H, W = int(rgb.shape[0]), int(rgb.shape[1])
+    if isinstance(aov, dict):
+        aov = cat([aov["albedo"].reshape(H * W, 3), aov["normal"].reshape(H * W, 3),
+                   aov["depth"].reshape(H * W, 1), aov["hit"].reshape(H * W, 1)], 1)
+    same = lambda a: isinstance(a, type(rgb)) and (isinstance(a, np.ndarray) or a.device == rgb.device)
+    if not same(aov) or aov.dtype != f64 or aov.shape[-1] != 8 or int(np.prod(aov.shape)) != H * W * 8:
+        raise ValueError("aov: render_aov's dict, or an (H, W, 8) or (npix, 8) float64 array of rgb's kind")
+    if var is not None and (not same(var) or var.dtype != f64 or int(np.prod(var.shape)) != H * W):
+        raise ValueError("var: an (H, W) float64 array of rgb's kind")
+    if ids is not None and (not same(ids) or ids.dtype != i32 or ids.shape[-1] != 4 or int(np.prod(ids.shape)) != H * W * 4):
+        raise ValueError("ids: an (H, W, 4) int32 array of rgb's kind")
+    prm = abi.rt_temporal_params(width=W, height=H, precision=abi.RT_PREC_F64 if rgb.dtype == f64 else abi.RT_PREC_F32,
+                                 on_device=on_device, flags=abi.RT_TEMPORAL_DEMODULATE if demodulate else 0,
+                                 max_history=max_history, alpha_min=alpha_min, depth_tol=depth_tol,
+                                 normal_cos=normal_cos, min_weight=min_weight, albedo_eps=albedo_eps)
+    if hist is not None and (not same(hist) or hist.dtype != u8 or hist.ndim != 1 or
+                             int(hist.shape[0]) != _history_bytes(prm)):
+        raise ValueError("hist: the hist of a call on a frame of this size and dtype")
+    opt = lambda a: None if a is None else contiguous(a)
+    return prm, contiguous(rgb), contiguous(aov), opt(var), opt(ids), opt(hist), ptr
+
+
+def history_planes(hist, W, H, dtype):
+    """Views of the four planes of a history buffer (include/rt_hip.h, "temporal accumulation"), a 1-D uint8 numpy
+    array or torch tensor: dict(color (H, W, 4) {c.r, c.g, c.b, v}, guide (H, W, 4) {n.x, n.y, n.z, z}, count (H, W),
+    id (H, W) int32), the first three of `dtype` (rgb's)."""
+    if isinstance(hist, np.ndarray):
+        size, i32 = np.dtype(dtype).itemsize, np.int32
+    else:
+        import torch
+        size, i32 = torch.empty((), dtype=dtype).element_size(), torch.int32
+    n = W * H
+    plane = lambda lo, hi, dt, *shape: hist[lo:hi].view(dt).reshape(*shape)
+    return dict(color=plane(0, 4 * size * n, dtype, H, W, 4), guide=plane(4 * size * n, 8 * size * n, dtype, H, W, 4),
+                count=plane(8 * size * n, 9 * size * n, dtype, H, W),
+                id=plane(9 * size * n, 9 * size * n + 4 * n, i32, H, W))
+
+
+def temporal_host(cam, prev_cam, rgb, feat, var=None, ids=None, hist=None, alpha_min=0.05, max_history=64,
+                  depth_tol=0.05, normal_cos=0.9, min_weight=0.25, demodulate=True, albedo_eps=1e-2):
+    """Context.temporal run by a host loop over the kernel's own arithmetic (rt_dev_temporal_host): numpy arrays, the
+    same dict back. No GPU, no Context; a development helper for tests."""
+    prm, rgb, feat, var, ids, hist, ptr = _temporal_inputs(rgb, feat, var, ids, hist, 0, alpha_min, max_history,
+                                                           depth_tol, normal_cos, min_weight, demodulate, albedo_eps)
+    H, W = prm.height, prm.width
+    out, var_out = np.empty_like(rgb), np.empty((H, W), np.float64)
+    hist_out = np.empty(_history_bytes(prm), np.uint8)
+    st = abi.load().rt_dev_temporal_host(ctypes.byref(prm), ctypes.byref(cam),
+                                         None if prev_cam is None else ctypes.byref(prev_cam), ptr(rgb), ptr(feat),
+                                         ptr(ids), ptr(var), ptr(hist), ptr(hist_out), ptr(out), ptr(var_out))
+    if st != abi.RT_OK:
+        raise abi.RTError(st, "rt_dev_temporal_host: arguments rt_temporal refuses")
+    return dict(rgb=out, var=var_out, hist=hist_out, count=history_planes(hist_out, W, H, rgb.dtype)["count"])
+
+
+class TemporalAccumulator:
+    """Context.temporal over a sequence of frames: keeps the camera of the frame before and two history buffers that
+    ping-pong, so a caller's loop is one line per frame. `params`: Context.temporal's keyword parameters. For
+    progressive rendering (a still camera, samples split over calls with first_sample) pass alpha_min=0 and
+    normal_cos=-1: with the default normal_cos the pixels that straddle an edge keep no history (Context.temporal).
+
+        acc = rt_amd.TemporalAccumulator(ctx, alpha_min=0.1)
+        for cam in path:
+            out = acc.push(cam, frame(cam)["rgb"], aov(cam), var)   # -> Context.temporal's dict
+    """
+
+    def __init__(self, ctx, **params):
+        self.ctx, self.params = ctx, params
+        self.reset()
+
+    def reset(self):
+        """Forget the history: the next frame is a first frame."""
+        self.prev_cam, self.hist, self.frames, self._bufs = None, None, 0, [None, None]
+
+    def push(self, cam, rgb, aov, var=None, stream=None):
+        """`aov`: render_aov's dict (its "ids" are used) or its rows (no ids). The returned dict's "hist" and "count"
+        are views of one of the two buffers: they hold this frame's history until the push after the next one
+        overwrites them. Frames of another size, dtype or kind than the one before start again with new buffers."""
+        ids = aov.get("ids") if isinstance(aov, dict) else None
+        target = self._bufs[self.frames & 1]
+        fits = lambda b: (b is not None and isinstance(b, type(rgb)) and
+                          (isinstance(b, np.ndarray) or b.device == rgb.device) and int(b.shape[0]) == nbytes)
+        nbytes = int(abi.load().rt_temporal_history_bytes(
+            int(rgb.shape[1]), int(rgb.shape[0]), abi.RT_PREC_F64 if rgb.dtype.itemsize == 8 else abi.RT_PREC_F32))
+        if self.hist is not None and not fits(self.hist):
+            self.reset()
+            target = None
+        out = self.ctx.temporal(cam, self.prev_cam, rgb, aov, var=var, ids=ids, hist=self.hist, stream=stream,
+                                hist_out=target if fits(target) else None, **self.params)
+        keep = abi.rt_camera_desc()
+        ctypes.memmove(ctypes.byref(keep), ctypes.byref(cam), ctypes.sizeof(keep))  # (the caller may move `cam` on)
+        self._bufs[self.frames & 1] = out["hist"]
+        self.prev_cam, self.hist, self.frames = keep, out["hist"], self.frames + 1
+        return out
 
 
 def multi_plan(w, h, ndev, rank, tile_size=0):

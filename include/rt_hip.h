@@ -528,7 +528,8 @@ void rt_dev_adaptive_error(int32_t K, int32_t batch, const double* S, const doub
  *
  * rt_denoise filters a whole row-major width x height image with an edge-avoiding a-trous wavelet filter (Dammertz et
  * al. 2010) whose colour edge-stop scales with each pixel's own variance and which carries that variance from pass to
- * pass (Schied et al. 2017, SVGF). It is spatial and single-frame: no history, no motion vectors. No reference
+ * pass (Schied et al. 2017, SVGF). It is spatial and single-frame: no history, no motion vectors (the temporal half,
+ * reprojected accumulation over frames, is rt_temporal below, whose outputs feed this call). No reference
  * counterpart. It needs no scene.
  *
  * rgb_in: npix x 3 floats (RT_PREC_F32) or doubles (RT_PREC_F64), e.g. rt_render_tiles' or rt_render_adaptive's image.
@@ -573,6 +574,88 @@ rt_status rt_denoise_check(const rt_denoise_params* params, char* why, size_t n)
  * aligned to 16 bytes. On an error nothing is launched and nothing is written. */
 rt_status rt_denoise(rt_context* ctx, const rt_denoise_params* params, const void* rgb_in, const double* feat,
                      const double* var, void* rgb_out, void* stream);
+
+/* ---- temporal accumulation: last frame's accumulated image reprojected into this frame ----
+ *
+ * rt_temporal is the temporal half of SVGF (Schied et al. 2017): it reprojects the accumulated image of the frame
+ * before into this frame through the two cameras and this frame's depth, rejects history that no longer shows the
+ * same surface, blends, and hands on a variance that has shrunk accordingly. Static scenes only: between the frames
+ * the camera moves, the objects do not. No reference counterpart. It needs no scene. Whole row-major width x height
+ * images, as for rt_denoise; T is float (RT_PREC_F32) or double (RT_PREC_F64).
+ *
+ * Inputs of this frame: rgb_in npix x 3 T; feat npix x 8 doubles, rt_render_aov's rows; ids npix x 4 int32,
+ * rt_render_aov's out_ids, of which only `object` is read, or NULL; var npix doubles, rt_denoise's var (the summed
+ * variance of the three channel means), or NULL.
+ * History: caller-owned, rt_temporal_history_bytes bytes, four planes in this order:
+ *   npix records {c.r, c.g, c.b, v}  4 T   the accumulated demodulated colour and the variance of a channel of it
+ *   npix records {n.x, n.y, n.z, z}  4 T   the guides of the frame that wrote it (a miss pixel: n = 0, z = -1)
+ *   npix counts N                    T     the frames accumulated, 0 = no usable history
+ *   npix object ids                  int32 (-2 = unknown: ids was NULL)
+ * hist_in == NULL is a first frame: no pixel has history, and prev_cam may be NULL. hist_in and hist_out must not
+ * overlap (the call gathers from one while it writes the other). The caller swaps the two between frames.
+ * Outputs: rgb_out npix x 3 T, may be rgb_in; var_out npix doubles or NULL, may be var.
+ *
+ * Per pixel p = (x, y). Steps 1 and 4 and the sums of step 3 are in T; step 2, the bilinear weights and the tests
+ * of step 3 are in double for both precisions.
+ * 1. The current sample. a = rt_denoise's albedo factor (albedo + albedo_eps per channel with
+ *    RT_TEMPORAL_DEMODULATE, else 1); c_cur = rgb / a; v_cur = var / 3 / mean(a)^2, or 1 with var == NULL; n, z as
+ *    rt_denoise prepares them: hit > 0: n = normal / hit, z = depth / hit; else n = 0, z = -1, a miss pixel. The
+ *    pixel's id is ids' object, or -2 with ids == NULL.
+ * 2. Where p was. If *cam and *prev_cam are byte-equal: (fx, fy) = (x, y) and z' = z exactly, for every camera mode.
+ *    Otherwise both are RT_CAM_PERSPECTIVE with the image size of params (anything else: RT_ERR_UNSUPPORTED), and
+ *      d_c = focal_length dir + ((x + 0.5) / W - 0.5) viewport_width right + (0.5 - (y + 0.5) / H) viewport_height up
+ *    (the direction of the pixel's camera ray with a zero jitter). A hit pixel sees X = pos + d_c / |d_c| z (the depth
+ *    is a distance); r = X - prev.pos and z' = |r|. A miss pixel sees the point at infinity: r = d_c. With
+ *    A = r . dir' / |dir'|^2 and B, C the same against right' and up' of prev_cam: A <= 0, or an fx or fy that is not
+ *    finite: no history. Otherwise
+ *      fx = (B f' / A / vw' + 0.5) W - 0.5,   fy = (0.5 - C f' / A / vh') H - 0.5.
+ * 3. The taps: the four pixels q = (floor(fx) + i, floor(fy) + j), i, j in 0 .. 1 (j outer, i inner), with their
+ *    bilinear weights w_q; a tap with w_q == 0 or outside the image is skipped. A tap is valid when its {c, v} is
+ *    finite, N_q > 0 and: for a miss pixel p, q is a miss pixel (z_q < 0); for a hit pixel p, q is a hit pixel with
+ *    |z_q - z'| <= depth_tol z', n_p . n_q >= normal_cos, and an equal object id or either id unknown.
+ *    Wv = sum of w_q over the valid taps. History exists when Wv >= min_weight and Wv > 0; then
+ *      c_h = sum w_q c_q / Wv,   v_h = sum w_q^2 v_q / Wv^2 (rt_denoise's rule),   N_h = sum w_q N_q / Wv.
+ * 4. The blend. With history: alpha = max(alpha_min, 1 / (N_h + 1)), c = (1 - alpha) c_h + alpha c_cur,
+ *    v = (1 - alpha)^2 v_h + alpha^2 v_cur, N = min(N_h + 1, max_history). Without: c = c_cur, v = v_cur, N = 1.
+ *    If c_cur or v_cur is not finite the frame contributes nothing: with history c, v, N = c_h, v_h, N_h; without,
+ *    the record is stored as it is with N = 0, so it is never a valid tap later.
+ * 5. The history record of p in hist_out is {c, v}, {n, z} of this frame, N and the pixel's id;
+ *    rgb_out = c a; var_out = 3 mean(a)^2 v.
+ *
+ * Consequences. With byte-equal cameras, the same feat, alpha_min = 0, normal_cos = -1 and max_history above the
+ * frame count, the output of frame k is the running mean of the k inputs and N = k (progressive rendering over
+ * first_sample), and var_out is the exact variance of that mean under independence: the mean of the k var divided by
+ * k. var_out has var's meaning and feeds rt_denoise unchanged. (normal_cos = -1 because n is rt_render_aov's mean
+ * over the pixel's samples, not a unit vector: where a pixel straddles an edge n . n < 1, and a normal_cos near 1
+ * rejects such a pixel's own history. On a moving camera that costs the edge pixels their history and nothing else.)
+ *
+ * on_device = 1: every pointer is a device pointer aligned to 16 bytes and the call is ordered on `stream` like
+ * rt_denoise; 0: host pointers, the call returns when the outputs and hist_out are filled. The launch stays on the
+ * caller's stream. Whole images only: with several GPUs, accumulate the gathered frame.
+ * Adds exactly 1 to rt_counters.launches and nothing else. */
+#define RT_TEMPORAL_DEMODULATE 1
+typedef struct rt_temporal_params {
+  int32_t width, height, precision, on_device, flags, max_history;
+  double alpha_min, depth_tol, normal_cos, min_weight, albedo_eps;
+} rt_temporal_params; /* 64 bytes, no padding */
+/* The rules alone, on the host (no device). The parameters: sides in [1, 65535] with width * height < 2^31, a known
+ * precision, flags within RT_TEMPORAL_DEMODULATE, max_history >= 1, alpha_min in [0, 1], depth_tol finite and > 0,
+ * normal_cos in [-1, 1], min_weight in [0, 1), albedo_eps finite and >= 0, > 0 when demodulating: else
+ * RT_ERR_INVALID_ARGUMENT, as for a null params or cam. The cameras, when prev_cam is not NULL: step 2's rule, else
+ * RT_ERR_UNSUPPORTED. The reason goes to why (n bytes). */
+rt_status rt_temporal_check(const rt_temporal_params* params, const rt_camera_desc* cam, const rt_camera_desc* prev_cam,
+                            char* why, size_t n);
+/* The bytes of a history of that size and precision, width * height * (9 sizeof(T) + 4); 0 for sides or a precision
+ * rt_temporal_check refuses. */
+size_t rt_temporal_history_bytes(int32_t width, int32_t height, int32_t precision);
+/* RT_ERR_INVALID_ARGUMENT: a null pointer (ids, var, hist_in, var_out excepted; prev_cam only with hist_in == NULL),
+ * parameters rt_temporal_check refuses, hist_in and hist_out that overlap, device pointers not aligned to 16 bytes;
+ * RT_ERR_UNSUPPORTED: cameras that differ and are not both perspective cameras of the image's size. On an error
+ * nothing is launched and nothing is written. */
+rt_status rt_temporal(rt_context* ctx, const rt_temporal_params* params, const rt_camera_desc* cam,
+                      const rt_camera_desc* prev_cam, const void* rgb_in, const double* feat, const int32_t* ids,
+                      const double* var, const void* hist_in, void* hist_out, void* rgb_out, double* var_out,
+                      void* stream);
 
 /* ---- multi-GPU driver: the framebuffer tiled over the devices of one node ----
  *
